@@ -14,6 +14,11 @@ driver's `--steps 20` is a multi-second timed region.
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
 
+A plain run sets up, warms up, times the K steps and prints the line (`ms_per_step` = milliseconds of one timed step).  `--full` adds
+everything else the line used to carry: the per-kernel HIP-event profile and roofline (its events ride inside the timed region), the step
+spread and clocks, the library's default three streams, small batches, the host-fed rate, the CPU baseline with its parity sample and, with
+--gpus N > 1, the strong-scaling leg.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
+
 Multi-GPU: each rank owns an independent IQ stream with its own demodulators (BASELINE config 5 style partitioning:
 no data-path collective); value = samples processed by all ranks / max-over-ranks time; scaling = weak.
 `--config C4 --gpus N` is the demodulator-sharded one-stream case (see cubicsdr_amd/parallel.py).
@@ -346,6 +351,53 @@ def spread(v):
     return {"n": len(s), "min": s[0], "median": s[len(s) // 2], "max": s[-1]} if s else {}
 
 
+DUMP_BUDGET = 64 << 20        # --dump-outputs: bytes written in all
+DUMP_SEED = 0x5EED            # the fixed sample of demodulators and spectrum frames
+
+
+def dump_outputs(dirname, bank, n_demods, spec=None, n_frames=0):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the last batch's per-block counts, IQ and audio of the
+    demodulators and the spectrum's display frames -- as DIR/<name>.npy in float32 / float64, at most DUMP_BUDGET bytes:
+      demod_counts (demods, blocks, 2: n_iq, n_audio), iq_tail (demods, K, 2), audio_tail (demods, K): every demodulator;
+      demods_sampled + iq_d<i> (n, 2) + audio_d<i>: the whole batch of a fixed, seeded sample of demodulators;
+      spectrum_frame_index + spectrum_frames (frames, 2 fftSize) + spectrum_center_floor (frames, 2): a fixed, seeded sample of frames, the last among them.
+    The same arguments give the same inputs and the same sample, so two builds of the project can be compared file for file.  -> bytes written"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    files = {}
+    res = [bank.results(i) for i in range(n_demods)]
+    counts = np.full((n_demods, max(len(r) for r in res), 2), -1.0)
+    for i, r in enumerate(res):
+        counts[i, :len(r)] = [(b.n_iq, b.n_audio) for b in r]
+    files["demod_counts"] = counts
+    iq = [bank.iq(i).view(np.float32).reshape(-1, 2) for i in range(n_demods)]
+    audio = [bank.audio(i) for i in range(n_demods)]
+    k_iq, k_au = min(256, min(len(a) for a in iq)), min(1024, min(len(a) for a in audio))
+    files["iq_tail"] = np.stack([a[len(a) - k_iq:] for a in iq])
+    files["audio_tail"] = np.stack([a[len(a) - k_au:] for a in audio])
+    room, picked = 24 << 20, []
+    for i in sorted(rng.choice(n_demods, size=min(16, n_demods), replace=False).tolist()):
+        if iq[i].nbytes + audio[i].nbytes <= room:
+            room -= iq[i].nbytes + audio[i].nbytes
+            picked.append(i)
+            files["iq_d%d" % i], files["audio_d%d" % i] = iq[i], audio[i]
+    files["demods_sampled"] = np.array(picked, np.float64)
+    if spec is not None and n_frames > 0:
+        k = max(1, min(16, n_frames, (24 << 20) // (8 * spec.fft_size)))
+        frames = sorted(set(rng.choice(n_frames - 1, size=k - 1, replace=False).tolist()) | {n_frames - 1}) if n_frames > 1 else [0]
+        got = [spec.fetch(f) for f in frames]
+        files["spectrum_frame_index"] = np.array(frames, np.float64)
+        files["spectrum_frames"] = np.stack([g[0] for g in got])
+        files["spectrum_center_floor"] = np.array([g[1:] for g in got], np.float64)
+    total = sum(a.nbytes for a in files.values())
+    assert total <= DUMP_BUDGET, total
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    for name, a in files.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return total
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: re-run this command line under torch.distributed.run, one rank per GPU of this node
     (rendezvous on 127.0.0.1, a free port); rank 0 prints the one JSON line.  Never returns."""
@@ -398,7 +450,17 @@ def main():
                     help="signal: noise + one modulated carrier per demodulator + DC (default, SURVEY.md 8d); noise: the noise and DC only "
                          "(counter-collection passes: rocprofv3 --pmc does not survive the thousands of small torch launches of the synthesis)")
     ap.add_argument("--no-strong", action="store_true", help="--gpus N > 1, default configuration: skip the strong-scaling leg (C4, time slabs) that follows the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline figure (profile and roofline, step spread, clocks, three streams, small batches, "
+                         "host-fed rate, CPU baseline and parity sample, strong scaling); the --no-* / --cpu-seconds switches above apply inside it.  "
+                         "Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at most 64 MB: dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_profile, args.no_latency, args.cpu_seconds, args.no_strong = True, True, 0.0, True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)                         # (does not return)
     line_out = claim_stdout()
@@ -431,7 +493,7 @@ def main():
     else:
         torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
-    sensors = Sensors(local_rank)
+    sensors = Sensors(local_rank) if args.full else None
 
     from cubicsdr_amd.engine import Context, DemodBank, SDRPost, SpectrumProcessor
     if args.ring == "noise":
@@ -474,7 +536,8 @@ def main():
         dist.barrier()
     if not args.no_profile:
         ctx.profile_enable(PROFILE_PERIOD)
-    sensors.start()
+    if sensors:
+        sensors.start()
     ctx.timer_start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -483,7 +546,7 @@ def main():
     ctx.synchronize()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    clocks = sensors.stop()
+    clocks = sensors.stop() if sensors else None
     if dist:
         dist.barrier()
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -494,10 +557,13 @@ def main():
         prof.update(ctx.profile())
         prof_rng = ctx.profile_range()
         ctx.profile_enable(False)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, bank, N_DEMODS, spec, spec._l.csdr_spec_frames(spec.h))
     audio_total = bank.total_audio()
     # the spread behind the mean: the same steps once more, each synchronised and timed on its own (after the timed region, which runs unbroken)
     step_ms = []
-    for _ in range(min(args.steps, 10)):
+    for _ in range(min(args.steps, 10) if args.full else 0):
         ts = time.perf_counter()
         step()
         ctx.synchronize()
@@ -516,11 +582,14 @@ def main():
                    "timed_region_s": elapsed, "event_ms_per_step": ev_ms / args.steps,
                    "error_metric": "parity tests hold |gpu - reference| <= 1e-5 of the reference's peak magnitude per compared array (tests/util.py rel_err); integer items bit-exact",
                    "streams": streams,
-                   "step_ms": dict(spread(step_ms), note="the same step run again after the timed region, each synchronised on its own"),
-                   "clocks": dict(clocks, note="amdgpu hwmon of this GPU sampled every 0.1 s inside the timed region (the kernels are issue-bound: their durations follow sclk, "
-                                               "which differs from box to box and ramps for ~40 ms after idle: profiles/r05_variance.txt)"),
                    "parallelism": "one independent IQ stream per GPU; stages of the timed pipeline on %d HIP stream(s)" % streams},
     }
+    if args.full:
+        out["config"]["step_ms"] = dict(spread(step_ms), note="the same step run again after the timed region, each synchronised on its own")
+        out["config"]["clocks"] = dict(clocks, note="amdgpu hwmon of this GPU sampled every 0.1 s inside the timed region (the kernels are issue-bound: their durations "
+                                                    "follow sclk, which differs from box to box and ramps for ~40 ms after idle: profiles/r05_variance.txt)")
+    if dumped is not None:
+        out["config"]["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
     if prof:
         units = NB * BLOCK                      # input samples one batch covers
         n_batches = args.steps * NBATCH
@@ -721,7 +790,7 @@ def main():
             sargs = argparse.Namespace(**vars(args))
             sargs.shard, sargs.blocks, sargs.batches, sargs.steps, sargs.warmup = "auto", 32, 6, max(2, min(args.steps, 5)), 1
             sargs.ingest, sargs.overlap = "distributed", True
-            sargs.no_profile, sargs.cpu_seconds, sargs.streams = True, 0.0, 3
+            sargs.no_profile, sargs.cpu_seconds, sargs.streams, sargs.dump_outputs = True, 0.0, 3, None
             so = sharded_bench.measure(sargs, dist=dist)
             out["strong"] = {"workload": so["config"]["workload"], "value": so["value"], "unit": "MS/s", "scaling": "strong", "n_gpus": world,
                              "ms_per_step": so["ms_per_step"], "steps": sargs.steps, "transport": so["config"]["transport"], "rccl_ranks": so["config"]["rccl_ranks"],

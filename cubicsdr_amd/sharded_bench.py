@@ -184,6 +184,10 @@ def measure(args, dist=None):
                                 "avg_launch_ms": avg[dom], "launches_per_batch": lpb, "algorithmic_bytes_per_launch": alg,
                                 "profile_sampling": "HIP events around every %d-th launch of each kernel id on rank 0, inside the timed region" % profile_period,
                                 "kernels_ms_per_batch": {k: per_batch[k] for k in sorted(per_batch, key=lambda k: -per_batch[k])}})
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        # rank 0's demodulators after the last timed step (bench.py dump_outputs; C4 has no spectrum)
+        import bench
+        out["config"]["dump_outputs"] = {"dir": args.dump_outputs, "bytes": bench.dump_outputs(args.dump_outputs, st.bank, len(st.plan.demods))}
     st.close()
     if rank == 0 and world == 1 and args.cpu_seconds > 0:
         # CPU baseline on a bounded sample of the same workload: the M = 1024 firpfbch over every block and 64 of the 1024 NBFM chains

@@ -590,10 +590,15 @@ class RefSpectrum:
         res = np.concatenate([mag[N // 2:], mag[:N // 2]]).astype(np.float64)                       # :450-451
         if getattr(self, "is_view", False) and self.new_resampler and self.last_view:
             self._rescale_averagers()
-        self.maa += (self.ma - self.maa) * self.rate                     # :494-497
+        nan = np.isnan(self.maa)                                         # :494-497: an averager that went NaN restarts from this frame's magnitude
+        self.maa[nan] = res[nan]
+        self.maa += (self.ma - self.maa) * self.rate
+        nan = np.isnan(self.ma)
+        self.ma[nan] = res[nan]
         self.ma += (res - self.ma) * self.rate
-        fft_ceil = np.float32(max(0.0, self.maa.max()))                  # float locals :436, :499-504
-        fft_floor = np.float32(min(1.0, self.maa.min()))
+        fin = self.maa[~np.isnan(self.maa)]                              # a NaN bin never wins a comparison: ceiling / floor over the others
+        fft_ceil = np.float32(max(0.0, fin.max()) if fin.size else 0.0)  # float locals :436, :499-504
+        fft_floor = np.float32(min(1.0, fin.min()) if fin.size else 1.0)
         self.ceil_ma += (float(fft_ceil) - self.ceil_ma) * 0.05          # :513-516
         self.ceil_maa += (self.ceil_ma - self.ceil_maa) * 0.05
         self.floor_ma += (float(fft_floor) - self.floor_ma) * 0.05       # :518-521

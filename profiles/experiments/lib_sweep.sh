@@ -1,19 +1,19 @@
 #!/bin/bash
 # usage: lib_sweep.sh OUTFILE lib-label ...   (label 0 = the in-tree library, else scratch/abl/lib<label>.so)
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
-OUT=gpurun_out/$1; shift
+mkdir -p bench_out
+OUT=bench_out/$1; shift
 : > $OUT
 for n in "$@"; do
   if [ $n = 0 ]; then LIB=$(pwd)/cubicsdr_amd/libcsdr_hip.so; else LIB=$(pwd)/scratch/abl/lib$n.so; fi
-  python - "$LIB" $n >> $OUT 2>gpurun_out/lib_sweep_$n.err <<'PY'
+  python - "$LIB" $n >> $OUT 2>bench_out/lib_sweep_$n.err <<'PY'
 import sys, json, io, runpy, contextlib
 import cubicsdr_amd.hip as H
 H.LIB_PATH = sys.argv[1]
 import cubicsdr_amd.build as B
 B.build = lambda *a, **k: None
 label = sys.argv[2]
-sys.argv = ["bench.py", "--steps", "4", "--warmup", "1", "--cpu-seconds", "0", "--no-latency"]
+sys.argv = ["bench.py", "--full", "--steps", "4", "--warmup", "1", "--cpu-seconds", "0", "--no-latency"]
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
     try:
