@@ -13,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+import tests.test_gpu_fft_exact as X
 import tests.test_gpu_parity as G
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -300,3 +301,18 @@ def test_emu_spectrum_sizes_that_are_not_powers_of_two(ctx):
     G.test_spectrum_points_first_frame_mode(ctx, 375, 4000)
     G._spectrum_contiguous_batches(ctx, 375, 2400000, (5, 3, 4))
     G._spectrum_contiguous_batches(ctx, 1500, 2400000, (5, 3, 4))
+
+
+@pytest.mark.parametrize("F", [pytest.param(F, marks=full if F > 65536 else ()) for F in X.SIZES])
+def test_emu_fft_exact_against_float64(ctx, F):
+    """every transform plan against a float64 DFT, bin by bin (tests/test_gpu_fft_exact.py): a wrong twiddle entry, index or table of a plan fails
+    here without a GPU; fftSize above 65536 (about 5 s per input at 2^21, 40 s at 1048575) in the full suite"""
+    import tests.test_gpu_fft_exact as X
+    X.check_fft_exact(ctx, F, quiet=True)
+
+
+@pytest.mark.parametrize("F", [pytest.param(F, marks=full if F > 65536 else ()) for F, _ in X.DISPLAY_SIZES])
+def test_emu_spectrum_display_points_against_float64(ctx, F):
+    """contiguous frames over three calls (frame 0 of a call split by the carry at an odd offset), the fused 2^17 chain included: display points
+    within the transform bound carried through the display arithmetic"""
+    X.check_display_exact(ctx, F)

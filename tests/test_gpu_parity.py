@@ -7,7 +7,7 @@ half-band buffer fill) bit-exact; float32 samples within 1e-5 of the reference's
 import numpy as np
 import pytest
 
-from tests.util import demod_frequencies, rel_err, synth_iq, synth_iq_fast
+from tests.util import demod_frequencies, exact_spectrum, rel_err, synth_iq, synth_iq_fast
 
 pytestmark = pytest.mark.gpu
 
@@ -759,10 +759,7 @@ def test_spectrum_line_cadence_overlapped_frames(ctx, F, line):
     want = []
     exact = None
     if F >= 65536:
-        class ExactSpectrum(RefSpectrum):                  # the same restatement with a float64 transform
-            def fft(self, frame):
-                return np.fft.fft(np.asarray(frame, dtype=np.complex128))
-        exact = ExactSpectrum(_backend(), F)
+        exact = exact_spectrum(_backend(), F)             # the same restatement with a float64 transform
     exact_all = []
     for k in range(nl):
         fr = ref.select_input(x[k * line:(k + 1) * line])
@@ -1152,12 +1149,7 @@ def _spectrum_contiguous_batches(ctx, F, fs, frames_per_batch, against_exact=Fal
         # profiles/experiments/spectrum_2m_sensitivity.py), i.e. 1e-5 .. 4e-5 of display value: at this size the reference itself is not within
         # 1e-5 of the exact result.  So the same frames also go through the restatement with a FLOAT64 transform, and the HIP path has to be as
         # close to that as the reference's own class is (and within TOL + both distances of the reference).
-        from oracle.cubicsdr_chain import RefSpectrum
-
-        class ExactSpectrum(RefSpectrum):
-            def fft(self, frame):
-                return np.fft.fft(np.asarray(frame, dtype=np.complex128))
-        exact = ExactSpectrum(_backend(), F)
+        exact = exact_spectrum(_backend(), F)
     sp = SpectrumProcessor(ctx, F, max_frames=max(frames_per_batch) + 1)
     pos = done = 0
     worst = worst_c = worst_ref_exact = worst_hip_exact = 0.0
