@@ -51,13 +51,8 @@ def _unit_deps(src):
 
 def build(force=False, verbose=True):
     build_design(force, verbose)
-    lab = os.environ.get("CSDR_BUILD_LAB") == "1"      # measurement build: the A/B switches of common.hpp lab_int() read the environment
     os.makedirs(OBJ_DIR, exist_ok=True)
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + (["-DCSDR_LAB"] if lab else [])
-    stamp = os.path.join(OBJ_DIR, "flavor")
-    flavor = "lab" if lab else "ship"
-    if not os.path.exists(stamp) or open(stamp).read() != flavor:
-        force = True
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
     jobs = []
     for src in SRCS:
         obj = os.path.join(OBJ_DIR, os.path.basename(src)[:-4] + ".o")
@@ -76,7 +71,6 @@ def build(force=False, verbose=True):
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max(1, min(len(jobs), os.cpu_count() or 1))) as ex:
         list(ex.map(compile_one, jobs))
-    open(stamp, "w").write(flavor)
     cmd = [cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-ldl", "-o", OUT]
     if verbose:
         print("[build]", " ".join(cmd), flush=True)

@@ -51,17 +51,6 @@ inline int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-// measurement switches (A/B runs recorded under profiles/): compiled in only with -DCSDR_LAB (CSDR_BUILD_LAB=1 python -m cubicsdr_amd.build);
-// the shipping library reads none of them
-inline int lab_int(const char *name, int dflt) {
-#ifdef CSDR_LAB
-    if (const char *e = getenv(name)) return atoi(e);
-#else
-    (void)name;
-#endif
-    return dflt;
-}
-
 // roctx ranges around the stage calls of the C ABI (csdr_post_execute, csdr_bank_execute, csdr_spec_process, the collectives): named spans
 // on the host timeline next to the kernel trace (rocprofv3 --marker-trace --kernel-trace).  Off unless CSDR_ROCTX=1 is set when the first
 // context is created: the tracing library (rocprofiler-sdk's roctx, else roctracer's) is then loaded with dlopen; nothing is linked.
@@ -421,14 +410,11 @@ struct ProfScope {
     do { ProfScope ps__((ctx_), (kid_), (ctx_)->lanes[lane_]); hipLaunchKernelGGL(kern_, grid_, block_, lds_, (ctx_)->lanes[lane_], __VA_ARGS__); } while (0)
 
 // streaming-hint stores / loads for data that is written or read once per launch and far exceeds the caches: the spectrum chain's outputs
-// (radix intermediate, magnitudes, pair sums, display values) and the radix pass's input.  Measured on C3 (-DCSDR_NT=0 compiles them as
-// plain accesses): radix 0.357 -> 0.347 ms, rows 0.286 -> 0.270 ms, average 0.186 -> 0.178 ms.  The same hint on the loads of the row
+// (radix intermediate, magnitudes, pair sums, display values) and the radix pass's input.  Measured on C3 against plain
+// accesses: radix 0.357 -> 0.347 ms, rows 0.286 -> 0.270 ms, average 0.186 -> 0.178 ms.  The same hint on the loads of the row
 // pass (the intermediate) costs it 10 %, on the averaging / display loads it changes nothing: those stay plain.
-#ifndef CSDR_NT
-#define CSDR_NT 1
-#endif
 namespace csdr {
-#if defined(__AMDGCN__) && CSDR_NT
+#if defined(__AMDGCN__)
 typedef float csdr_nt2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void st_stream(float *p, float v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ void st_stream(float2 *p, float2 v) { const csdr_nt2 t = {v.x, v.y}; __builtin_nontemporal_store(t, reinterpret_cast<csdr_nt2 *>(p)); }

@@ -252,9 +252,6 @@ extern "C" int csdr_bank_set_active(csdr_bank *b, int slot, int active) {
 // 32 consecutive lanes are the progression (theta0 + 2 p dtheta) >> 22: the rotation with the fewest addresses per bank, over a fixed set of starting
 // phases and both samples of a lane's pair.  A layout choice only: any value computes the same samples.
 static uint32_t fe_table_rotation(uint32_t dtheta) {
-#ifdef CSDR_FE_NOROT
-    return 0;                                                      // (A/B builds: the plain table order)
-#endif
     if (!dtheta) return 0;
     uint32_t best = 0;
     int best_cost = 1 << 30;
@@ -464,7 +461,7 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
             int n5 = 0, n6 = 0;
             for (int i = 0; i < n_run; ++i) { const int d = key[3 * (size_t)i + 2]; n5 += d == 5; n6 += d == 6; }
             const int fe_resident = std::max(1, c->wg_slots(demod_frontend_s56<2048>, kFeThreads + 64, fes_lds_bytes<6, 2048>()));      // (memoised per context: another device, another answer)
-            const bool merge56 = n5 > 0 && n6 > 0 && 4 * (n5 + n6) <= fe_resident && lab_int("CSDR_FE_MERGE56", 1) != 0;
+            const bool merge56 = n5 > 0 && n6 > 0 && 4 * (n5 + n6) <= fe_resident;
             b->grp_merged56 = merge56;
             auto klass = [&](int i) { const int d = key[3 * (size_t)i + 2]; return (d == 5 && merge56) ? 6 : d; };
             std::vector<int> &list = b->grp_list;
@@ -547,8 +544,7 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
     // ranges per slot, PER LAUNCH (the slots are grouped by cascade depth, one launch per group on the same stream): as many as
     // make that launch's grid ONE round of resident workgroups (each range re-runs `warm` inputs, so fewer, longer ranges
     // waste less), but never shorter than 4 warm-up spans and never fewer than one
-    static const int fe_pct = std::max(10, std::min(100, lab_int("CSDR_FE_PCT", 100)));
-    const int fe_slots = std::max(1, c->wg_slots(demod_frontend_s<5, 2048, true>, kFeThreads + 64, fes_lds_bytes<5, 2048>()) * fe_pct / 100);
+    const int fe_slots = std::max(1, c->wg_slots(demod_frontend_s<5, 2048, true>, kFeThreads + 64, fes_lds_bytes<5, 2048>()));
     auto ranges_for = [&](int n_slots) {
         int P = (int)std::max<int64_t>(1, std::min<int64_t>(total / std::max<int64_t>(4096, 4 * (int64_t)warm_max), 4096));
         const int per_slot = fe_slots / std::max(1, n_slots) - 1;                          // one extra workgroup per slot carries the histories
@@ -637,15 +633,13 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
         CSDR_LAUNCH(c, LANE_FE, KID_FE_S##S_, (demod_frontend_s<S_, CH_>), dim3(16, grp_rows[S_] * (ranges_for(grp_n[S_]) + 1)), dim3(kFeThreads), (fes_lds_bytes<S_, CH_>()), \
                     b->cfgs.p, dyns_d, grp_d + grp_off[S_], chan_out, post->chan_stride, total, b->arms.p, c->sintab.p, grp_rows[S_])
     CSDR_FE_S(3, 2048); CSDR_FE_S(4, 2048);
-    static const bool tw6 = lab_int("CSDR_FE_TW6", 1) != 0;
-    if (grp_n[6] > 0) {          // depth 6 (AM / SSB from ~500 kS/s channels): tail wave with three tail stages (CSDR_FE_TW6=0: without)
+    if (grp_n[6] > 0) {          // depth 6 (AM / SSB from ~500 kS/s channels): tail wave with three tail stages
         if (merged56)
             CSDR_LAUNCH(c, LANE_FE, KID_FE_S56, (demod_frontend_s56<2048>), dim3(16, grp_rows[6] * (ranges_for(grp_n[6]) + 1)), dim3(kFeThreads + 64), (fes_lds_bytes<6, 2048>()),
                         b->cfgs.p, dyns_d, grp_d + grp_off[6], chan_out, post->chan_stride, total, b->arms.p, c->sintab.p, grp_rows[6]);
-        else if (tw6)
+        else
             CSDR_LAUNCH(c, LANE_FE, KID_FE_S6, (demod_frontend_s<6, 2048, true>), dim3(16, grp_rows[6] * (ranges_for(grp_n[6]) + 1)), dim3(kFeThreads + 64), (fes_lds_bytes<6, 2048>()),
                         b->cfgs.p, dyns_d, grp_d + grp_off[6], chan_out, post->chan_stride, total, b->arms.p, c->sintab.p, grp_rows[6]);
-        else CSDR_FE_S(6, 2048);
     }
     if (grp_n[7] > 0) {          // interpolating IQ resamplers: chunks of output samples
         int64_t jmax = 0;

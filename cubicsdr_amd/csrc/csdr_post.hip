@@ -53,15 +53,8 @@ extern "C" void csdr_post_destroy(csdr_post *p) {
     delete p;
 }
 
-#ifndef CSDR_P2_MX_MIN_A
-#define CSDR_P2_MX_MIN_A 11           // critically sampled bank: the smallest A whose transforms go to the matrix pipe (M = 22 ... 62: 1.03 - 1.25 x the vector form, which keeps M = 6 / 10 / 14: profiles/r06_mx_channelizer.txt)
-#endif
-#ifndef CSDR_P2_OS2_MIN_A
-#define CSDR_P2_OS2_MIN_A 19          // firpfbch2 with M / 2 odd: the smallest A = M / 2 that takes chan_analyze_p2 (M >= 38: 1.2 - 2.5 x the two-factor kernel, which wins below: profiles/r06_chan2_p2.txt)
-#endif
-#ifndef CSDR_CHAN_MX_DEFAULT
-#define CSDR_CHAN_MX_DEFAULT 1          // (A/B builds: -DCSDR_CHAN_MX_DEFAULT=0 keeps the vector form of chan_analyze_p2's transform phase for every A)
-#endif
+constexpr int kP2MxMinA = 11;         // critically sampled bank: the smallest A whose transforms go to the matrix pipe (M = 22 ... 62: 1.03 - 1.25 x the vector form, which keeps M = 6 / 10 / 14: profiles/r06_mx_channelizer.txt)
+constexpr int kP2Os2MinA = 19;        // firpfbch2 with M / 2 odd: the smallest A = M / 2 that takes chan_analyze_p2 (M >= 38: 1.2 - 2.5 x the two-factor kernel, which wins below: profiles/r06_chan2_p2.txt)
 // geometry of the channelizer kernel for M channels (see kernels_post.hpp)
 static int chan_geometry(int M, int hop, ChanGeom &g) {
     memset(&g, 0, sizeof g);
@@ -84,9 +77,9 @@ static int chan_geometry(int M, int hop, ChanGeom &g) {
     // faster); firpfbch2 (hop == M / 2: every frame but one in two starts at an odd sample offset) for every odd A, in the kernel's matrix-pipe form with
     // the two lattices of frames dealt to its waves.
     const bool twice_odd = (M & 3) == 2 && M / 2 >= 3 && M / 2 <= kP2MaxA;
-    const bool p2_os2 = twice_odd && M / 2 >= CSDR_P2_OS2_MIN_A && hop * 2 == M && CSDR_CHAN_MX_DEFAULT && lab_int("CSDR_CHAN_P2_OS2", 1);
+    const bool p2_os2 = twice_odd && M / 2 >= kP2Os2MinA && hop * 2 == M;
     if (p2_os2) { g.B = 2; g.A = M / 2; g.oddA = 1; }
-    if ((p2_os2 || (hop == M && g.B == 2 && g.oddA && g.A <= kP2MaxA)) && !lab_int("CSDR_CHAN_GENERIC", 0)) {
+    if (p2_os2 || (hop == M && g.B == 2 && g.oddA && g.A <= kP2MaxA)) {
         // whole transform of a frame inside one lane (kernels_post.hpp, chan_analyze_p2): (A - 1) / 2 output pairs + the k = 0
         // pseudo pair, split evenly over (up to) four passes of at most eight slots
         const int slots = (g.A - 1) / 2 + 1;
@@ -96,7 +89,7 @@ static int chan_geometry(int M, int hop, ChanGeom &g) {
         g.PA = g.nkA * g.KA;
         g.TF = kP2Frames; g.lgTF = 6; g.S = M; g.taps_lds = 0; g.stage_in = 1; g.threads = kP2Threads;
         // the A-point transforms on the fp32 matrix pipe (A >= 11; below 33 one row tile of sixteen outputs: half of the waves sit the phase out)
-        g.mx = (hop != M || (g.A >= CSDR_P2_MX_MIN_A && lab_int("CSDR_CHAN_MX", CSDR_CHAN_MX_DEFAULT) != 0)) ? 1 : 0;
+        g.mx = (hop != M || g.A >= kP2MxMinA) ? 1 : 0;
         return CSDR_OK;
     }
     g.taps_lds = (M <= 512) ? 1 : 0;
@@ -125,18 +118,9 @@ typedef void (*chan_kernel_t)(const float2 *, const float2 *, float2 *, const fl
 typedef void (*chan_p2_kernel_t)(const float2 *, const float2 *, float2 *, const float *, const float2 *, const float2 *, const int *, ChanGeom,
                                  int64_t, float2 *, int64_t, d2 *, double, const float2 *);
 static chan_p2_kernel_t chan_p2_kernel(const ChanGeom &g) {
-#define CSDR_P2_CASE(K_) case K_: return chan_analyze_p2<K_>
     // (A <= 63: at most 32 slots over eight waves = at most four per pass; wider passes were instances nothing ever launched -- one of them spilled)
     if (g.mx) return g.hop != g.M ? chan_analyze_p2<4, true, true> : chan_analyze_p2<4, true>;
-#if CSDR_CHAN_MX_DEFAULT == 0 || defined(CSDR_LAB)      // (A/B builds: the vector form for every A)
-    switch (g.KA) {
-        CSDR_P2_CASE(1); CSDR_P2_CASE(2); CSDR_P2_CASE(3);
-        default: return chan_analyze_p2<4>;
-    }
-#else
     return chan_analyze_p2<1>;                          // A <= 9: at most five slots over eight waves
-#endif
-#undef CSDR_P2_CASE
 }
 typedef void (*chanfft_kernel_t)(const float2 *, const float2 *, float2 *, const float *, const float2 *, const int *, const int *, ChanFftGeom, int64_t,
                                  float2 *, int64_t, d2 *, double, const float2 *);
@@ -145,7 +129,7 @@ static chanfft_kernel_t chanfft_kernel(const ChanFftGeom &g) {
     if (g.wide_odd) return chan_analyze_fft<true, false>;
     if (g.bp) return chan_analyze_fft<false, false, 4>;            // a prime factor >= 157: the instance with the chirp-z pass
     if (g.dp) return chan_analyze_fft<false, false, 5>;            // a prime factor 29 .. 151: the instance with the direct prime pass
-    switch (lab_int("CSDR_CHANFFT_PLAN", 1) ? cf_plan_of(g) : 0) {      // the BASELINE channel counts have an instance of their own (only their radices: fewer registers)
+    switch (cf_plan_of(g)) {      // the BASELINE channel counts have an instance of their own (only their radices: fewer registers)
         case 1: return chan_analyze_fft<false, false, 1>;
         case 2: return chan_analyze_fft<false, false, 2>;
         case 3: return chan_analyze_fft<false, false, 3>;
@@ -192,10 +176,7 @@ extern "C" int csdr_post_configure(csdr_post *p, int64_t sample_rate, int num_ch
         if (!(q & 1)) ++q;
         p->chan_stride = q * 16;
     }
-    if (lab_int("CSDR_ROW_PAD", 1) == 0) p->chan_stride = ((int64_t)max_blocks * (max_block_len / p->hop) + 1) & ~(int64_t)1;      // the round-3 pitch (A/B)
-    const int out_off_kb = std::min(8192, lab_int("CSDR_OUT_OFFSET_KB", -1));                                  // (measurement build: where the output starts inside its allocation;
-    p->out_off = (size_t)std::max(0, out_off_kb) * 128;                                        //  the allocation itself is the same for every offset up to 8 MB)
-    if (int rc = p->out.reserve((size_t)p->chan_stride * M * csdr_post::kPostBufs + (out_off_kb >= 0 ? (size_t)1 << 20 : 0))) return rc;
+    if (int rc = p->out.reserve((size_t)p->chan_stride * M * csdr_post::kPostBufs)) return rc;
     if (int rc = p->dc_state.reserve(2)) return rc;
     CSDR_HIP_TRY(hipMemsetAsync(p->dc_state.p, 0, 2 * sizeof(d2), st));
     p->dc_parity = 0;
@@ -208,12 +189,11 @@ extern "C" int csdr_post_configure(csdr_post *p, int64_t sample_rate, int num_ch
     if (mode != CSDR_POST_SINGLE) {
         if (int rc = chan_geometry(M, p->hop, p->geom)) return rc;
         const ChanGeom &g = p->geom;
-        // every channel count that is not 2 * odd and factors over the small radices takes the FFT kernel (kernels_chanfft.hpp);
-        // CSDR_CHAN_FFT=0 keeps the two-factor direct-DFT kernel (A/B measurements, bit-for-bit routing tests)
+        // every channel count that is not 2 * odd and factors over the small radices takes the FFT kernel (kernels_chanfft.hpp)
         std::vector<int> fperm;
         // (firpfbch2 too, since round 5: the oversampled hop is two interleaved lattices of frames in the same kernel, M % 4 == 0)
-        p->use_fft = (mode == CSDR_POST_PFBCH || mode == CSDR_POST_PFBCH2) && !g.p2 && lab_int("CSDR_CHAN_FFT", 1) != 0 &&
-                     chanfft_plan(M, (size_t)p->ctx->lds_per_cu, lab_int("CSDR_CHANFFT_TF", 0), lab_int("CSDR_CHANFFT_THREADS", 0), p->fgeom, fperm, mode == CSDR_POST_PFBCH2);
+        p->use_fft = (mode == CSDR_POST_PFBCH || mode == CSDR_POST_PFBCH2) && !g.p2 &&
+                     chanfft_plan(M, (size_t)p->ctx->lds_per_cu, p->fgeom, fperm, mode == CSDR_POST_PFBCH2);
         // prototype taps transposed to [n][c]: tapsT[n M + c] multiplies x[(t - n) M + c]
         std::vector<float> taps = mode == CSDR_POST_PFBCH2 ? design::channelizer2_taps((unsigned)M, 4, 60.0f)      // initPFBCH2 :463
                                                            : design::channelizer_taps((unsigned)M, 4, 60.0f);      // initPFBCH :406
@@ -254,7 +234,7 @@ extern "C" int csdr_post_configure(csdr_post *p, int64_t sample_rate, int num_ch
             if (int rc = p->perm.reserve(fperm.size())) return rc;
             CSDR_HIP_TRY(hipMemcpyAsync(p->perm.p, fperm.data(), fperm.size() * sizeof(int), hipMemcpyHostToDevice, st));
             if (p->fgeom.bp || p->fgeom.dp) {      // tables of the chirp-z / direct prime pass: they travel in the place of firpfbch2's post factors (never both)
-                const std::vector<float2> bt = p->fgeom.bp ? chanfft_blue_tables(p->fgeom) : kCfPrimeMx ? chanfft_direct_mx_tables(p->fgeom) : chanfft_direct_tables(p->fgeom);
+                const std::vector<float2> bt = p->fgeom.bp ? chanfft_blue_tables(p->fgeom) : chanfft_direct_mx_tables(p->fgeom);
                 if (int rc = p->post2.reserve(bt.size())) return rc;
                 CSDR_HIP_TRY(hipMemcpy(p->post2.p, bt.data(), bt.size() * sizeof(float2), hipMemcpyHostToDevice));
             }
@@ -398,21 +378,17 @@ extern "C" int csdr_post_execute(csdr_post *p, const float *iq, int iq_is_dev, i
         const bool fused_ends = dc0 && g.fpw >= 16;
         if (p->use_fft) {
             // persistent workgroups (as many as are resident at once) walk over the tiles
-            ChanFftGeom fg = p->fgeom;
-            fg.xcd = lab_int("CSDR_CHANFFT_XCD", fg.xcd);
+            const ChanFftGeom &fg = p->fgeom;
             const size_t lds = chanfft_lds_bytes(fg);
             const chanfft_kernel_t kf = chanfft_kernel(fg);
-            const int wgs = std::min(ntiles, std::max(1, c->wg_slots(kf, fg.threads, lds) * lab_int("CSDR_CHANFFT_PCT", 100) / 100));
+            const int wgs = std::min(ntiles, std::max(1, c->wg_slots(kf, fg.threads, lds)));
             CSDR_LAUNCH(c, LANE_POST, KID_CHAN_ANALYZE, kf, dim3(wgs), dim3(fg.threads), lds, x, hist, hist_new, p->taps.p,
                         p->twM.p, p->perm.p, p->active.p, fg, n_frames, out, p->chan_stride, fused_ends ? p->tile_end.p : (d2 *)nullptr, p->dc_c,
                         (p->mode == CSDR_POST_PFBCH2 || fg.bp || fg.dp) ? p->post2.p : (const float2 *)nullptr);
         } else if (g.p2) {
             // persistent workgroups: as many as are resident at once, each walks over tiles blockIdx.x, + gridDim.x, ...
             const chan_p2_kernel_t k2 = chan_p2_kernel(g);
-            const int chan_pct = std::max(10, std::min(100, lab_int("CSDR_CHAN_PCT", 100)));
-            const int wgs = std::min(ntiles, std::max(1, c->wg_slots(k2, g.threads, chan_p2_lds_bytes(M, g.mx != 0, g.hop != M)) * chan_pct / 100));
-            g.xcd = lab_int("CSDR_CHAN_XCD", g.xcd);
-            if (lab_int("CSDR_LAB_TRACE", 0)) fprintf(stderr, "[csdr lab] chan_analyze_p2 x=%p out=%p hist=%p taps=%p cs=%p twM=%p wgs=%d xcd=%d\n", (const void *)x, (void *)out, (void *)hist, (void *)p->taps.p, (void *)p->twA.p, (void *)p->twM.p, wgs, g.xcd);
+            const int wgs = std::min(ntiles, std::max(1, c->wg_slots(k2, g.threads, chan_p2_lds_bytes(M, g.mx != 0, g.hop != M))));
             CSDR_LAUNCH(c, LANE_POST, KID_CHAN_ANALYZE, k2, dim3(wgs), dim3(g.threads), chan_p2_lds_bytes(M, g.mx != 0, g.hop != M), x, hist, hist_new, p->taps.p,
                         p->twA.p, p->twM.p, p->active.p, g, n_frames, out, p->chan_stride, fused_ends ? p->tile_end.p : (d2 *)nullptr, p->dc_c,
                         p->mode == CSDR_POST_PFBCH2 ? p->post2.p : (const float2 *)nullptr);

@@ -75,7 +75,7 @@ struct csdr_spec {
     DevBuf<float2> peakf;
     bool view_frame = false;                 // the frames being post-processed belong to the zoomed view
     bool fused_ok = false;                   // N = 2^17: the 512 x 256 chain with the averaging fused into the row pass exists (kernels_spec3.hpp)
-    bool fused_now = false;                  // ... and this batch takes it (full-span view, no peak hold set or pending)
+    bool fused_now = false;                  // ... and this batch takes it (full-span view)
 };
 
 extern "C" int csdr_spec_create(csdr_ctx *ctx, csdr_spec **out) {
@@ -193,7 +193,7 @@ extern "C" int csdr_spec_setup(csdr_spec *s, int fft_size, int max_frames) {
         g.Ra = std::min(R, 32); g.Rb = R / g.Ra;
         // 2^21 points: ONE 512-point column pass through LDS (spec_cols512, kernels_spec2.hpp) instead of a radix-32 and a radix-16 pass through
         // HBM -- 16 instead of 32 B/sample in front of the 4096-point rows; bins k = k1 + 512 k3, row = k1 (the layout of Ra = 512, Rb = 1)
-        if (N == kC512 * 4096 && lab_int("CSDR_SPEC_COLS512", 1) != 0) { g.Ra = kC512; g.Rb = 1; }
+        if (N == kC512 * 4096) { g.Ra = kC512; g.Rb = 1; }
     }
     g.lgRa = ilog2(g.Ra); g.lgRb = ilog2(g.Rb);
     s->max_frames = max_frames;
@@ -210,9 +210,8 @@ extern "C" int csdr_spec_setup(csdr_spec *s, int fft_size, int max_frames) {
     CSDR_HIP_TRY(hipMemcpy(s->tw_hi.p, hi.data(), hi.size() * sizeof(float2), hipMemcpyHostToDevice));
     const size_t nfN = (size_t)max_frames * N, F = (size_t)g.F;
     if (g.Ra == kC512) CSDR_HIP_TRY(hipFuncSetAttribute((const void *)spec_cols512, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kC512Lds));
-    // the headline size: two passes with the averaging fused into the second (30 instead of 38 B per sample; CSDR_SPEC_FUSED=0 of the measurement
-    // build keeps the three-kernel chain for A/B runs)
-    s->fused_ok = N == kS3N && !npot && lab_int("CSDR_SPEC_FUSED", 1) != 0;
+    // the headline size: two passes with the averaging fused into the second (30 instead of 38 B per sample)
+    s->fused_ok = N == kS3N && !npot;
     if (s->fused_ok) {
         CSDR_HIP_TRY(hipFuncSetAttribute((const void *)spec_cols512p, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kP1Lds));
         CSDR_HIP_TRY(hipFuncSetAttribute((const void *)spec_rows256_ema<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kR2Lds));
@@ -395,11 +394,9 @@ static int spec_post_range(csdr_spec *s, const float *mag, int f0, int cnt, int 
         CSDR_HIP_TRY(hipGetLastError());
         return CSDR_OK;
     }
-    // frame groups per workgroup: up to 16 frames each, so a short batch does not pay the set-up of sixteen groups
-    // (CSDR_AVG_GROUPS = 4 | 8 | 16 caps the groups: fewer, smaller workgroups let two of them share a CU -- one loads its round while the
-    // other scans)
-    static const int avg_cap = std::max(1, std::min(kAvgGroups, lab_int("CSDR_AVG_GROUPS", kAvgGroupsDefault)));
-    const int avg_groups = std::max(1, std::min(avg_cap, (cnt + kAvgGMax - 1) / kAvgGMax));      // (fewer frames per group -- 8 / 4 / 2 -- measured on C5's 25-frame batches: 0.22 -> 0.25 - 0.27 ms)
+    // frame groups per workgroup: up to 16 frames each, so a short batch does not pay the set-up of sixteen groups; at most kAvgGroupsDefault:
+    // fewer, smaller workgroups let two of them share a CU -- one loads its round while the other scans
+    const int avg_groups = std::max(1, std::min(kAvgGroupsDefault, (cnt + kAvgGMax - 1) / kAvgGMax));      // (fewer frames per group -- 8 / 4 / 2 -- measured on C5's 25-frame batches: 0.22 -> 0.25 - 0.27 ms)
     CSDR_LAUNCH(c, LANE_AVG, KID_SPEC_AVG, spec_average, dim3(s->n_avg_tiles), dim3(kAvgLanes * avg_groups), avg_lds_bytes(avg_groups), mag + (size_t)f0 * g.N, cnt, g, (double)s->avg_rate,
                 s->ma.p, s->maa.p, s->pairsum.p + f0 * F, s->first_b.p + f0, s->ext_w.p + (size_t)f0 * s->n_avg_tiles,
                 bins ? s->maaf.p + f0 * F : (float2 *)nullptr, view ? 0 : (hold ? pk_from : cnt));
@@ -709,9 +706,9 @@ extern "C" int csdr_spec_process(csdr_spec *s, const float *iq, int iq_is_dev, i
     hipStream_t st = c->lanes[LANE_FFT];
     const SpecGeom &g = s->g;
     const int N = g.N;
-    // full-span view: the 512 x 256 chain with the averaging fused into its row pass (since round 6 with peak hold too: CSDR_SPEC_FUSED_HOLD=0 is the
-    // earlier rule -- a batch with peak hold set or pending on the three-kernel chain)
-    s->fused_now = s->fused_ok && ((!s->peak_hold && s->peak_reset == 0) || lab_int("CSDR_SPEC_FUSED_HOLD", 1) != 0);
+    // full-span view: the 512 x 256 chain with the averaging fused into its row pass (since round 6 with peak hold too; the earlier rule sent a
+    // batch with peak hold set or pending to the three-kernel chain)
+    s->fused_now = s->fused_ok;
     const int64_t n = (int64_t)n_blocks * block_len;
     const float2 *x = (const float2 *)iq;
     if (int rc = c->lane_begin(LANE_FFT)) return rc;

@@ -32,13 +32,7 @@ namespace csdr {
 constexpr int kCfMaxPasses = 8;
 constexpr int kCfSeg = 8;                 // frames one FIR work item produces
 constexpr int kCfMaxThreads = 1024;
-#ifndef CSDR_CF_PRIO_FIR
-#define CSDR_CF_PRIO_FIR 2
-#endif
-#ifndef CSDR_CF_PRIO_PASS
-#define CSDR_CF_PRIO_PASS 1
-#endif
-constexpr int kCfPrioFir = CSDR_CF_PRIO_FIR, kCfPrioPass = CSDR_CF_PRIO_PASS;      // (A/B builds: -DCSDR_CF_PRIO_FIR=0 -DCSDR_CF_PRIO_PASS=0 is the round-5 kernel)
+constexpr int kCfPrioFir = 2, kCfPrioPass = 1;      // wave priorities of the FIR phase and of the passes (both 0 was the round-5 kernel)
 
 struct ChanFftGeom {
     int M, TF, lgTF, TFs;                 // TFs: row pitch of X in samples (TF + 2)
@@ -57,24 +51,15 @@ struct ChanFftGeom {
     int bp, bL, blgL;                     // 0: no such factor
     int bnpass, bradix[4], bspan[4];      // the bL-point transform: radices 16 / 8 / 4 / 2, span of sub-pass k inside bL
     // a prime factor 29 .. 199: pass 0 is its direct transform in the conjugate-pair form of chan_analyze_p2's transform phase, out of place into a second
-    // tile -- on the fp32 matrix pipe (cf_prime_pass_mx; the vector form -- lane = (column, frame), wave = four output pairs, (cos, sin) rows wave-uniform -- is
-    // kept for A/B builds)
-    int dp, dnk, dPA;                     // the prime (0: none), groups of four output-pair slots, pitch of a (cos, sin) row
-    unsigned magic_s0;                    // floor(2^32 / (M / dp)) + 1
+    // tile, on the fp32 matrix pipe (cf_prime_pass_mx)
+    int dp;                               // the prime (0: none)
+    int unused_[3];                       // (what the retired vector form of that pass read: kept, so that the kernel arguments keep their offsets)
 };
-constexpr int kCfDirectKP = 4;
-#ifndef CSDR_CF_PRIME_MX
-#define CSDR_CF_PRIME_MX 1
-#endif
-constexpr bool kCfPrimeMx = CSDR_CF_PRIME_MX != 0;      // the direct prime pass on the fp32 matrix pipe (A/B builds: -DCSDR_CF_PRIME_MX=0 is the vector form)
 // (measured, profiles/r06_chirpz_channel_counts.txt: the convolution costs 2.2 - 2.6 x the factor's own data in LDS work space and six trips through it;
 //  against the VECTOR form of the direct prime pass it won from p ~ 157 on.  Against the matrix-pipe form of that pass (cf_prime_pass_mx,
 //  profiles/r06_prime_mx.txt) it loses for every prime the fragments' registers reach -- M = 314: 1.27 against 0.67 ms, M = 398: 1.06 against 0.73 ms --
 //  so it now starts at p = 211, i.e. M >= 422: beyond the counts getOptimalChannelCount returns for rates up to 200 MS/s)
-#ifndef CSDR_CF_BLUE_MIN
-#define CSDR_CF_BLUE_MIN 211
-#endif
-constexpr int kCfBlueMinPrime = CSDR_CF_BLUE_MIN, kCfBlueMaxPrime = 509;
+constexpr int kCfBlueMinPrime = 211, kCfBlueMaxPrime = 509;
 
 __host__ __device__ inline size_t chanfft_lds_bytes(const ChanFftGeom &g) {
     // (oversampled: + the M post factors; chirp-z pass: + the work array of M / bp transforms of bL points per frame, W_bL, the transformed chirp, the chirp)
@@ -84,8 +69,7 @@ __host__ __device__ inline size_t chanfft_lds_bytes(const ChanFftGeom &g) {
 
 // plan for M channels: radices (odd ones first, then the powers of two from the widest), tile size, workgroup size.
 // Returns false when M has a prime factor this kernel has no butterfly for (chan_analyze takes those).
-// (force_tf / force_threads: measurement overrides, 0 = automatic)
-__host__ inline bool chanfft_plan(int M, size_t lds_limit, int force_tf, int force_threads, ChanFftGeom &g, std::vector<int> &perm, bool os2 = false) {
+__host__ inline bool chanfft_plan(int M, size_t lds_limit, ChanFftGeom &g, std::vector<int> &perm, bool os2 = false) {
     memset(&g, 0, sizeof g);
     g.M = M; g.os2 = os2 ? 1 : 0;
     if (os2 && (M & 3)) return false;             // the half-frame offset M / 2 of the second lattice must keep the column pairs 16-byte aligned
@@ -102,12 +86,8 @@ __host__ inline bool chanfft_plan(int M, size_t lds_limit, int force_tf, int for
         bool prime = m >= 29 && m <= kCfBlueMaxPrime;
         for (int d = 3; prime && d * d <= m; d += 2) prime = m % d != 0;
         if (!prime || os2 || g.wide_odd) return false;
-        if (m < kCfBlueMinPrime) {                // the direct pass
-            g.dp = m;
-            const int H = (m - 1) / 2;
-            g.dnk = (H + 1 + kCfDirectKP - 1) / kCfDirectKP; g.dPA = g.dnk * kCfDirectKP;
-            g.magic_s0 = (unsigned)((1ull << 32) / (unsigned)(M / m)) + 1u;
-        } else g.bp = m;
+        if (m < kCfBlueMinPrime) g.dp = m;        // the direct pass
+        else g.bp = m;
         g.blgL = 0; while ((1 << g.blgL) < 2 * m - 1) ++g.blgL;
         g.bL = 1 << g.blgL;
         g.bnpass = (g.blgL + 3) / 4;
@@ -145,7 +125,6 @@ __host__ inline bool chanfft_plan(int M, size_t lds_limit, int force_tf, int for
         if ((M / g.dp) * tf < 64 && fits(2 * tf)) { tf *= 2; dp_wide = true; }
     }
     if (g.bp) { tf = M >= 280 ? 16 : 8; while (tf > kCfSeg && !fits(tf)) tf >>= 1; }      // chirp-z plans: small tiles, several workgroups per CU (sweep in profiles/r06_chirpz_channel_counts.txt)
-    if (force_tf >= kCfSeg && !(force_tf & (force_tf - 1)) && fits(force_tf)) tf = force_tf;
     if (!fits(tf)) return false;
     g.lgTF = 0; while ((1 << g.lgTF) < tf) ++g.lgTF;
     if (os2 && tf < 2 * kCfSeg) return false;
@@ -154,7 +133,6 @@ __host__ inline bool chanfft_plan(int M, size_t lds_limit, int force_tf, int for
     while (g.threads < kCfMaxThreads && g.threads < fir_items) g.threads <<= 1;
     if (g.bp) g.threads = M >= 280 ? 1024 : 512;
     if (g.dp) g.threads = dp_wide ? 1024 : 512;
-    if (force_threads >= 64 && force_threads <= kCfMaxThreads && !(force_threads & 63)) g.threads = force_threads;
     g.xcd = M >= 64;             // (C4: + 5 %, M = 20: nothing)
     // pos = sum_p r_p s_p holds channel k = r_0 + R_0 (r_1 + R_1 (r_2 + ...)) after the last pass
     perm.assign(M, 0);
@@ -166,21 +144,9 @@ __host__ inline bool chanfft_plan(int M, size_t lds_limit, int force_tf, int for
     return true;
 }
 
-// (cos, sin)(2 pi k(q) c / p) of the direct prime pass at [(c - 1) dPA + q], c = 1 .. (p - 1) / 2; slot q: k = q + 1 (q < H), k = 0 (q == H: (1, 0)), (0, 0) beyond
-__host__ inline std::vector<float2> chanfft_direct_tables(const ChanFftGeom &g) {
-    const int p = g.dp, H = (p - 1) / 2;
-    std::vector<float2> t((size_t)H * g.dPA, make_float2(0.f, 0.f));
-    for (int c = 1; c <= H; ++c) for (int q = 0; q <= H; ++q) {
-        const int k = q < H ? q + 1 : 0;
-        const double a = 2.0 * M_PI * (double)(((int64_t)c * k) % p) / (double)p;
-        t[(size_t)(c - 1) * g.dPA + q] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    return t;
-}
-
-// The same pass on the fp32 matrix pipe (cf_prime_pass_mx): coefficient fragments [2 (cos | sin)][row tile][step][64 lanes] -- lane l of step J holds the
+// (cos, sin)(2 pi k n / p) of the direct prime pass on the fp32 matrix pipe (cf_prime_pass_mx): coefficient fragments [2 (cos | sin)][row tile][step][64 lanes] -- lane l of step J holds the
 // coefficient of output k = 16 rt + (l & 15) and term n = 4 J + (l >> 4), the A operand of v_mfma_f32_16x16x4_f32; term 0 is x_0 (cos = 1, sin = 0),
-// outputs and terms past H are zero.  The angles are the vector form's expression: the products are the same products.
+// outputs and terms past H are zero.
 __host__ __device__ inline int chanfft_mx_row_tiles(int p) { return ((p - 1) / 2 + 16) / 16; }      // outputs k = 0 .. H
 __host__ __device__ inline int chanfft_mx_steps(int p) { return ((p - 1) / 2 + 4) / 4; }            // terms n = 0 .. H, four per step
 constexpr int kCfMxMaxSteps = 25;                                                                   // p <= 199
@@ -449,70 +415,11 @@ __device__ __forceinline__ void cf_blue_pass(const ChanFftGeom &g, float2 *s_x, 
     for (int k = g.bnpass - 1; k >= 0; --k) { cf_blue_dispatch(g, k, true, s_x, s_ws, s_tw, s_wl, s_bh, s_c, tid, nthr); if (k) lds_barrier(); }
 }
 
-// pass 0 of a plan with a prime factor dp = 29 .. 89, rows j + s0 q of s_x -> rows j + s0 r of s_y:  y[r] = W_M^(j r) sum_q x[q] W_dp^(q r).
-// Step A forms s_c = x_c + x_{dp-c} and d_c = x_c - x_{dp-c} in place (rows c and dp - c of every column); step B is chan_analyze_p2's transform phase:
-// a lane owns one (column j, frame t), a wave four output-pair slots; P_k = x_0 + sum_c s_c cos, Q_k = sum_c d_c sin with the (cos, sin) rows wave-uniform
-// (scalar loads); y_k = P_k - j Q_k, y_{dp-k} = P_k + j Q_k, times the pass's twiddle, into the second tile (another wave still reads the first).
-template <int KP>
-__device__ __forceinline__ void cf_prime_pass(const ChanFftGeom &g, float2 *s_x, float2 *s_y, const float2 *s_tw, const float2 *__restrict__ cs, int tid, int nthr) {
-    const int TF = g.TF, TFs = g.TFs, p = g.dp, s0 = g.M / p, H = (p - 1) >> 1;
-    for (int it = tid; it < ((s0 * H) << g.lgTF); it += nthr) {
-        const int t = it & (TF - 1);
-        const unsigned rest = (unsigned)it >> g.lgTF, c1 = s0 == 1 ? rest : __umulhi(rest, g.magic_s0), j = rest - c1 * (unsigned)s0;
-        float2 *pa = s_x + (size_t)(j + s0 * (c1 + 1)) * TFs + t, *pb = s_x + (size_t)(j + s0 * (p - 1 - c1)) * TFs + t;
-        const float2 a = *pa, b = *pb;
-        *pa = make_float2(a.x + b.x, a.y + b.y); *pb = make_float2(a.x - b.x, a.y - b.y);
-    }
-    lds_barrier();
-    const int lane = tid & 63, wave = wave_uniform(tid >> 6), nw = nthr >> 6;
-    const int n_li = s0 << g.lgTF, lgroups = (n_li + 63) >> 6, tasks = lgroups * g.dnk;
-    for (int task = wave; task < tasks; task += nw) {
-        const int sg = task / lgroups, lg = task - sg * lgroups;          // (wave-uniform)
-        const int li = min(lg * 64 + lane, n_li - 1);
-        const bool live = lg * 64 + lane < n_li;
-        const int t = li & (TF - 1), j = li >> g.lgTF;
-        const float2 *col = s_x + (size_t)j * TFs + t;
-        const int rs = s0 * TFs;                                           // row c of this column: col + c rs
-        const float2 x0 = col[0];
-        float2 P[KP], Q[KP];
-#pragma unroll
-        for (int k = 0; k < KP; ++k) { P[k] = x0; Q[k] = make_float2(0.f, 0.f); }
-        const float2 *w = cs + sg * KP;
-        float2 sa = col[rs], da = col[(size_t)(p - 1) * rs];
-        for (int c = 1; c <= H; ++c) {
-            const int cn = min(c + 1, H);
-            const float2 sn = col[(size_t)cn * rs], dn = col[(size_t)(p - cn) * rs];      // the next term's rows, requested before this term's arithmetic
-            float2 e[KP];
-#pragma unroll
-            for (int k = 0; k < KP; ++k) e[k] = w[k];
-            w += g.dPA;
-#pragma unroll
-            for (int k = 0; k < KP; ++k) {
-                P[k].x = fmaf(sa.x, e[k].x, P[k].x); P[k].y = fmaf(sa.y, e[k].x, P[k].y);
-                Q[k].x = fmaf(da.x, e[k].y, Q[k].x); Q[k].y = fmaf(da.y, e[k].y, Q[k].y);
-            }
-            sa = sn; da = dn;
-        }
-        float2 *ycol = s_y + (size_t)j * TFs + t;
-#pragma unroll
-        for (int k = 0; k < KP; ++k) {
-            const int q = sg * KP + k;                                         // (wave-uniform)
-            if (q < H) {
-                const int kk = q + 1, kn = p - kk;
-                if (live) {
-                    ycol[(size_t)kk * rs] = cmul(make_float2(P[k].x + Q[k].y, P[k].y - Q[k].x), s_tw[j * kk]);      // j r < M
-                    ycol[(size_t)kn * rs] = cmul(make_float2(P[k].x - Q[k].y, P[k].y + Q[k].x), s_tw[j * kn]);
-                }
-            } else if (q == H) { if (live) ycol[0] = P[k]; }
-        }
-    }
-}
-
 // The direct prime pass on the fp32 matrix pipe.  P = Cos s and Q = Sin d are real matrix products per component (re / im), tiled 16 (k) x 16 (columns) x 4
 // (terms) on v_mfma_f32_16x16x4_f32: a wave takes (row tile of sixteen outputs, column tile of sixteen (column j, frame t) lanes); lane (q = lane >> 4,
 // i = lane & 15) feeds term n = 4 J + q of its column in step J -- s_n = x_n + x_{p-n} and d_n formed from the two rows as they are read, so step A and
-// its barrier are gone -- and receives outputs k = 16 rt + 4 q + r of that column.  An MFMA is a k-ordered fmaf chain: with the terms in ascending
-// order the sums are the vector form's, bit for bit.  The coefficient fragments of a wave's row tile (2 x steps registers) are fetched once per tile.
+// its barrier are gone -- and receives outputs k = 16 rt + 4 q + r of that column.  An MFMA is a k-ordered fmaf chain: the terms go in ascending
+// order, as in a plain fmaf loop.  The coefficient fragments of a wave's row tile (2 x steps registers) are fetched once per tile.
 __device__ __forceinline__ void cf_prime_pass_mx(const ChanFftGeom &g, float2 *s_x, float2 *s_y, const float2 *s_tw, const float *__restrict__ tab, int tid, int nthr) {
     const int TF = g.TF, TFs = g.TFs, p = g.dp, s0 = g.M / p, H = (p - 1) >> 1;
     const int RT = chanfft_mx_row_tiles(p), KS = chanfft_mx_steps(p);
@@ -807,8 +714,7 @@ CSDR_KERNEL __launch_bounds__(kCfMaxThreads) void chan_analyze_fft(
             float2 *dcs = dc_ends ? s_dc : nullptr;
             if constexpr (PLAN == 4) if (p == 0) { cf_blue_pass(g, s_x, s_ws, s_tw, s_wl, s_bh, s_c, tid, nthr); lds_barrier(); continue; }
             if constexpr (PLAN == 5) if (p == 0) {
-                if (kCfPrimeMx) cf_prime_pass_mx(g, s_x, s_ws, s_tw, reinterpret_cast<const float *>(post), tid, nthr);
-                else cf_prime_pass<kCfDirectKP>(g, s_x, s_ws, s_tw, post, tid, nthr);
+                cf_prime_pass_mx(g, s_x, s_ws, s_tw, reinterpret_cast<const float *>(post), tid, nthr);
                 lds_barrier(); s_t = s_ws; continue;
             }
 #define CSDR_CF_CASE(R_)                                                                                                                         \

@@ -210,7 +210,9 @@ struct ChanGeom {
     int threads;              // workgroup size (whole waves, 256..512): chosen so each phase splits evenly over the waves
     int p2;                   // 1: M = 2 A, A odd <= 63, critically sampled: chan_analyze_p2 (KA = slots per pass, nkA = passes, PA = row pitch)
     int mx;                   // chan_analyze_p2: 1 = the A-point transforms run on the fp32 matrix pipe (A >= 33: chan_analyze_p2<.., true>)
-    int xcd;                  // chan_analyze_p2: 1 = the workgroups of one XCD (blockIdx.x % 8) take CONSECUTIVE tiles of a round (grid a multiple of 8)
+    int xcd;                  // chan_analyze_p2: 1 = the workgroups of one XCD (blockIdx.x % 8) take CONSECUTIVE tiles of a round (grid a multiple of 8),
+                              // 2 = a contiguous range of tiles per workgroup.  The host leaves it 0 (neither paid: profiles/r05_variance.txt); the walks
+                              // stay because without them chan_analyze_p2<1> is allocated other register counts
 };
 __host__ __device__ inline size_t chan_zin_floats2(const ChanGeom &g) {      // Z array, or the staged input tile if larger
     const size_t z = (size_t)g.TF * g.S, in = g.stage_in ? (size_t)(g.TF - 1) * g.hop + (size_t)kChanTaps * g.M : 0;
@@ -525,23 +527,10 @@ CSDR_KERNEL __launch_bounds__(64 * kChanMaxWaves) void chan_analyze(
 // ------------------------------------------------------------------------------------------------------------
 constexpr int kP2Frames = 64;          // frames per tile (lane = frame in the DFT phase)
 constexpr int kP2Waves = 8;
-#ifndef CSDR_P2_PRIO_DFT
-#define CSDR_P2_PRIO_DFT 1
-#endif
-#ifndef CSDR_P2_REQ_PRIO
-#define CSDR_P2_REQ_PRIO 2
-#endif
-constexpr int kP2ReqPrio = CSDR_P2_REQ_PRIO;
-constexpr int kP2DftPrio = CSDR_P2_PRIO_DFT;            // (A/B builds: -DCSDR_P2_PRIO_DFT=0 is the round-5 kernel)
-#ifndef CSDR_P2_EARLY
-#define CSDR_P2_EARLY 8
-#endif
-constexpr int kP2EarlyRows = CSDR_P2_EARLY;          // rows of the next tile's FIR window requested before the DFT phase (the first frame's whole window); the other seven after it
+constexpr int kP2ReqPrio = 2;
+constexpr int kP2DftPrio = 1;                        // (0 was the round-5 kernel)
+constexpr int kP2EarlyRows = 8;                      // rows of the next tile's FIR window requested before the DFT phase (the first frame's whole window); the other seven after it
 constexpr int kP2Threads = 64 * kP2Waves;
-#ifndef CSDR_P2_MIRROR
-#define CSDR_P2_MIRROR 1
-#endif
-constexpr bool kP2Mirror = CSDR_P2_MIRROR != 0;          // matrix-pipe form: odd waves hold their FIR window in descending order (A/B builds: -DCSDR_P2_MIRROR=0)
 constexpr int kP2MaxA = 63;
 // (the matrix-pipe form keeps two small tables behind the rows: the per-output constants of its epilogue and the tile's channel-0 samples)
 constexpr int kMxSteps = 8;            // K steps of four terms: n = 0 .. 31 (H <= 31)
@@ -764,7 +753,8 @@ CSDR_KERNEL __launch_bounds__(kP2Threads, 4) void chan_analyze_p2(
         const int64_t per = (n_tiles + gridDim.x - 1) / gridDim.x;
         tile = (int64_t)blockIdx.x * per; tstep = 1; tend = min(n_tiles, tile + per);
     }
-    const bool mirw = MX && kP2Mirror && (((OS2 ? wave >> 1 : wave) & 1) != 0);      // (the neighbours that share rows: the next wave, oversampled the next wave of the same lattice)
+    // matrix-pipe form: odd waves hold their FIR window in descending order
+    const bool mirw = MX && (((OS2 ? wave >> 1 : wave) & 1) != 0);      // (the neighbours that share rows: the next wave, oversampled the next wave of the same lattice)
     chan_p2_request_window<0, 2 * kChanTaps - 1, OS2>(x, hist, M, A, n_frames, tile, tile < tend, wave, lane0, win, mirw);
     for (; tile < tend; tile += tstep) {
         const int64_t f0 = tile * kP2Frames;

@@ -380,7 +380,7 @@ CSDR_KERNEL_SPEC __launch_bounds__(kFftThreads) void spec_blue_post(const float2
 // forms (float max, float min) per frame and the wave (= 64 points of one frame) reduces them.
 constexpr int kAvgLanes = 64;
 constexpr int kAvgGroups = 16;             // most frame groups (waves) per workgroup
-constexpr int kAvgGroupsDefault = 8;       // what the host launches unless told otherwise: two workgroups share a CU (measured on C3: 16 / 8 / 4 groups = 0.213 / 0.186 / 0.189 ms)
+constexpr int kAvgGroupsDefault = 8;       // the most the host launches: two workgroups share a CU (measured on C3: 16 / 8 / 4 groups = 0.213 / 0.186 / 0.189 ms)
 constexpr int kAvgThreads = kAvgLanes * kAvgGroups;
 constexpr int kAvgGMax = 16;               // frames per thread per round -> 256 frames per round
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B helper (runs here, no GPU): profiles/mkvariant.sh NAME UNIT "FLAGS"  ->  _ab/NAME.so = the current library with unit UNIT (csdr_post | csdr_bank | csdr_spec ...)
-# recompiled with extra FLAGS (e.g. -DCSDR_P2_MIRROR=0).  The variants are compared on one box with profiles/ab_so.sh.
+# recompiled with extra FLAGS (e.g. -O2: they follow the build's own).  The variants are compared on one box with profiles/ab_so.sh.
 set -e
 cd "$(dirname "$0")/.."
 name=$1; unit=$2; flags=$3

@@ -21,8 +21,7 @@ def lib_path(flavor=""):
 def build(flavor="", force=False, verbose=False):
     """flavor: "" (plain -O2), "asan", "tsan" """
     os.makedirs(OUT_DIR, exist_ok=True)
-    lab = os.environ.get("CSDR_BUILD_LAB") == "1"       # the measurement switches of common.hpp lab_int() compiled in
-    out = lib_path(flavor + ("lab" if lab else ""))
+    out = lib_path(flavor)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if os.path.isfile(os.path.join(CSRC, f))] + [os.path.join(HERE, "hip", "hip_runtime.h"),
                                                                 os.path.join(HERE, "hip_emu_runtime.cpp"),
                                                                 os.path.join(ROOT, "include", "csdr_hip.h")]
@@ -30,8 +29,7 @@ def build(flavor="", force=False, verbose=False):
         return out
     san = {"": ["-O2"], "asan": ["-O1", "-g", "-fsanitize=address", "-fno-omit-frame-pointer"],
            "tsan": ["-O1", "-g", "-fsanitize=thread"]}[flavor]
-    cmd = ["g++", "-std=c++20", "-shared", "-fPIC", "-pthread", "-w", "-ffp-contract=off", "-I", HERE] + san + \
-          (["-DCSDR_LAB"] if lab else [])
+    cmd = ["g++", "-std=c++20", "-shared", "-fPIC", "-pthread", "-w", "-ffp-contract=off", "-I", HERE] + san
     units = sorted(f for f in os.listdir(CSRC) if f.startswith("csdr_") and f.endswith(".hip"))
     objs = []
 
