@@ -286,6 +286,7 @@ enum CsdrKernelId {
     KID_FE_GENERIC, KID_FE_S3, KID_FE_S4, KID_FE_S5, KID_FE_S6, KID_FE_S56, KID_FE_INTERP,
     KID_MODEM, KID_GAIN_SCAN, KID_FMS, KID_AUDIO, KID_FMS_OUT, KID_MIX, KID_TABLES,
     KID_FFT_COLS, KID_FFT_ROWS, KID_SPEC_AVG, KID_SPEC_TRACK, KID_SPEC_DISPLAY, KID_SPEC_MISC,
+    KID_DIGITAL,
     KID_COUNT
 };
 

@@ -105,13 +105,13 @@ extern "C" void csdr_bank_destroy(csdr_bank *b) {
         if (b->stage_ev[r]) (void)hipEventDestroy(b->stage_ev[r]);
     }
     b->bout_h.release();
-    b->pcm.release(); b->pcm_jobs.release();
+    b->pcm.release(); b->pcm_jobs.release(); b->dig_jobs.release();
     delete b;
 }
 
 // no device modem / audio stage: the internal front-end-only slot, or a host plug-in modem (CSDR_MODEM_HOST) that demodulates the fetched IQ
 static int modem_check_rate(int modem, int bw, int audio_rate) {   // Modem*::checkSampleRate (ModemAnalog.cpp:14-19, ModemUSB.cpp:29-37, ModemIQ.cpp:31-33)
-    if (modem == CSDR_MODEM_HOST) return bw;                       // the plug-in's own checkSampleRate ran on the host
+    if (modem == CSDR_MODEM_HOST || modem == CSDR_MODEM_DIGITAL) return bw;      // the plug-in's own checkSampleRate ran on the host; digital: csdr_digital.hip
     if (modem == CSDR_MODEM_IQ || modem == CSDR_MODEM_FRONTEND_ONLY) return audio_rate;
     if (modem == CSDR_MODEM_FMS) return bw < 100000 ? 100000 : bw;      // ModemFMStereo.cpp:27-35
     if (bw < 500) bw = 500;                          // MIN_BANDWIDTH, Modem.h:13
@@ -121,6 +121,7 @@ static int modem_check_rate(int modem, int bw, int audio_rate) {   // Modem*::ch
 
 extern "C" int csdr_bank_configure_slot(csdr_bank *b, int slot, const csdr_demod_params *prm, const csdr_post *post) {
     DeviceScope dev__(b ? b->ctx : nullptr);
+    if (prm && prm->modem == CSDR_MODEM_DIGITAL) return fail(CSDR_EINVAL, "CSDR_MODEM_DIGITAL slots are configured with csdr_bank_configure_digital_slot");
     if (prm && (prm->modem < CSDR_MODEM_NBFM || prm->modem > CSDR_MODEM_HOST)) return fail(CSDR_EUNSUPPORTED, "modem %d", prm->modem);
     return bank_configure_slot(b, slot, prm, post);
 }
@@ -133,6 +134,7 @@ int bank_configure_slot(csdr_bank *b, int slot, const csdr_demod_params *prm, co
     SlotHost &s = b->slots[slot];
     if (int rc = b->ctx->sync_all()) return rc;
     s.configured = false;
+    s.dig.reset();
     s.prm = *prm;
     s.prm.bandwidth = modem_check_rate(prm->modem, prm->bandwidth, prm->audio_sample_rate);
     s.chan_rate = csdr_post_channel_rate(post);
@@ -325,13 +327,17 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
             s.theta = q.theta; s.dtheta = q.dtheta; s.buf_idx = q.buf_idx; s.phase = q.phase; s.aphase = q.aphase; s.abuf = q.abuf; s.ssb_theta = q.ssb_theta;
             s.shift_frequency = q.shift_frequency; s.shift_valid = q.shift_valid; s.hist_parity = q.hist_parity; s.last_parity = q.last_parity; s.prev_J = q.prev_J;
             s.results.clear(); s.last_J = 0; s.last_A = 0;
+            if (s.dig) bank_digital_plan(b, si, 0, nullptr);
         }
+        b->dig_run.clear();
         b->stage_next = ring_before;
         return rc;
     };
+    b->dig_run.clear();
     for (int si = 0; si < b->max_demods; ++si) {
         SlotHost &s = b->slots[si];
         s.results.clear(); s.last_J = 0; s.last_A = 0;
+        if (s.dig) bank_digital_plan(b, si, 0, nullptr);          // (no blocks: nothing until the walk reaches it)
         if (!s.configured || !s.active) continue;
         if (s.chan_rate != rate) return reject(fail(CSDR_ESTATE, "slot %d was built for channel rate %lld, post now runs %lld: reconfigure", si, (long long)s.chan_rate, (long long)rate));
         // channel routing: runDemodChannels, SDRPostThread.cpp:317-323 (nearest centre; M == wrap channel = M/2)
@@ -361,6 +367,7 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
         s.results.resize(NB);
         if (skipped) {
             for (auto &r : s.results) { memset(&r, 0, sizeof r); r.skipped = 1; r.nco_theta = s.theta; r.resamp_phase = s.phase; r.buffer_index = s.buf_idx; }
+            if (s.dig) bank_digital_plan(b, si, NB, nullptr);
             continue;
         }
         SlotDyn &d = dyns_h[si];
@@ -424,6 +431,7 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
         s.hist_parity ^= 1;
         s.last_J = (int)Jtot; s.last_A = fe_only ? 0 : (int)(Qtot << ash);
         s.prev_J = (int)Jtot;
+        if (s.dig) bank_digital_plan(b, si, NB, pl);
         warm_max = std::max(warm_max, s.warm); max_aS = std::max(max_aS, aS);
         if (fms) fms_slots.push_back(si);
         else if (s.prm.modem != CSDR_MODEM_NBFM && s.prm.modem != CSDR_MODEM_FM && s.prm.modem != CSDR_MODEM_IQ && !fe_only) {
@@ -690,6 +698,8 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
         CSDR_LAUNCH(c, LANE_AUDIO, KID_FMS_OUT, fms_out, dim3(n_fms, NB), dim3(64), fms_out_lds, b->cfgs.p, dyns_d, fms_d, plans_d, NB, fms_au);
     }
     }
+    // digital slots: the decision kernel behind the front-end (not part of the modem / audio kernels above, nor of the fused one-block launch)
+    if (int rc = bank_digital_launch(b, plans_d, NB)) return rc;
     CSDR_HIP_TRY(hipGetLastError());
     if (int rc = c->signal(b->ev_audio_done[bpar], LANE_AUDIO, LANE_FE)) return rc;
     b->audio_pending[bpar] = true;

@@ -2,6 +2,7 @@
 // (the demodulator bank reads the channelizer's output rotation; the audio / scope edges read the bank's slots).
 #pragma once
 #include <map>
+#include <memory>
 #include <vector>
 
 #include "common.hpp"
@@ -55,6 +56,7 @@ static inline float2 *post_buf(const csdr_post *p, int k) { return p->out.p + (s
 
 // =================================================================================================== demodulator bank
 namespace csdr {
+struct DigSlot;                              // a digital slot's modem (csdr_digital.hip)
 struct SlotHost {
     bool configured = false, active = false;
     csdr_demod_params prm{};
@@ -79,6 +81,7 @@ struct SlotHost {
     // results of the last execute
     std::vector<csdr_block_result> results;
     int last_J = 0, last_A = 0;
+    std::shared_ptr<DigSlot> dig;            // CSDR_MODEM_DIGITAL: the decision stage behind the front-end
 };
 constexpr int kStageRing = 4;                // pinned staging sets for the per-batch uploads
 }  // namespace csdr
@@ -121,10 +124,17 @@ struct csdr_bank {
     std::vector<SnapBytes> snap;             // host-state snapshot of a batch being planned (a rejected batch puts it back)
     DevBuf<int16_t> pcm;                     // csdr_bank_fetch_pcm16: the converted audio of one slot
     DevBuf<PcmJob> pcm_jobs;
+    std::vector<int> dig_run;                // digital slots of the batch being planned (csdr_digital.hip)
+    DevBuf<char> dig_jobs;                   // their launch records
+    std::vector<char> dig_jobs_h;
 };
 
 // internal modem id: NCO + msresamp only, no modem / audio stage (the zoomed spectrum view's shift + resample, SpectrumVisualProcessor.cpp:306-379)
 #define CSDR_MODEM_FRONTEND_ONLY 100
 // csdr_bank_configure_slot without the public entry point's modem-range check (csdr_bank.hip; the zoomed view configures a front-end-only slot)
 int bank_configure_slot(csdr_bank *b, int slot, const csdr_demod_params *prm, const csdr_post *post);
-static inline bool is_fe_only(int modem) { return modem == CSDR_MODEM_FRONTEND_ONLY || modem == CSDR_MODEM_HOST; }
+static inline bool is_fe_only(int modem) { return modem == CSDR_MODEM_FRONTEND_ONLY || modem == CSDR_MODEM_HOST || modem == CSDR_MODEM_DIGITAL; }
+// digital slots (csdr_digital.hip): csdr_bank_execute plans each one's batch while it walks the slots (plan = the slot's block starts, NB + 1 of
+// them; nullptr: the slot is skipped this batch), and launches the decision kernel behind the front-end, on the modem / audio lane
+void bank_digital_plan(csdr_bank *b, int slot, int NB, const BlockPlan *plan);
+int bank_digital_launch(csdr_bank *b, const BlockPlan *plans_d, int NB);

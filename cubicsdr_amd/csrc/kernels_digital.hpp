@@ -1,0 +1,213 @@
+// kernels_digital.hpp -- the digital lab (reference src/modules/modem/digital/, built there with ENABLE_DIGITAL_LAB): per-sample hard decisions of
+// the modemcf constellations of ModemPSK / DPSK / ASK / QAM / BPSK / QPSK / OOK, and the fskdem symbols of ModemFSK, behind the front-end's
+// resampled IQ.  One launch covers every digital slot and every block of a batch.
+//
+// Replaces (reference file:line): Modem{PSK,DPSK,ASK,QAM}.cpp ::demodulate (the modemcf_demodulate loop and updateDemodulatorLock),
+// Modem{BPSK,QPSK,OOK}.cpp ::demodulate, ModemFSK.cpp:127-143 (inputBuffer, fskdem_demodulate per k samples).
+//
+// The constellations are computed here from their definitions (Gray-coded phase / amplitude levels, rectangular grids, unit mean energy); the
+// decision rules are the demodulator's own, not nearest-point: the phase is offset and quantised by successive approximation, amplitude levels and
+// the I / Q rails of a grid by successive-approximation thresholds each, DPSK quantises the phase difference to the previous input sample.
+#pragma once
+#include "common.hpp"
+#include "kernels_demod.hpp"
+
+namespace csdr {
+
+enum DigScheme : int32_t { DIG_PSK = 0, DIG_DPSK, DIG_ASK, DIG_QAM, DIG_BPSK, DIG_QPSK, DIG_OOK, DIG_FSK };
+
+constexpr int kDigThreads = 256;
+constexpr int kDigFskMaxK = 2048;          // fskdem samples per symbol (its create rule: k <= 2^11)
+constexpr int kDigStateFloats = 8;         // per constellation: r (2), x_hat (2), DPSK input phase, 3 spare
+
+// one constellation's decision geometry (host-computed from the definition: csdr_digital.hip dig_geometry)
+struct DigGeom {
+    int32_t scheme;       // DigScheme
+    int32_t m_i, m_q;     // bits on the phase / amplitude / I rail, bits on the Q rail (QAM)
+    float alpha;          // PSK / DPSK: pi / M (half the phase step); ASK / QAM: the level step that gives unit mean energy
+    float d_phi;          // PSK / DPSK: pi (1 - 1 / M), the phase offset taken off before quantising
+    float step;           // PSK / DPSK: 2 pi / M
+};
+
+// one digital slot's work in one launch
+struct DigJob {
+    const float2 *iq;         // this batch's resampled IQ (n samples)
+    int32_t n;                // samples of the batch
+    int32_t nb;               // blocks of the batch
+    const BlockPlan *plan;    // [nb + 1] block starts inside the batch (front-end plans; the standalone entry: one block)
+    uint32_t *sym;            // symbols out: one per sample (constellations), one per whole symbol (FSK)
+    float *bevm;              // [nb] per block: the EVM after the block (constellations)
+    const float *st_rd;       // the active constellation's state before the batch (kDigStateFloats)
+    float *st_wr;             // ... and after it (another copy: the first and the last workgroup may run at once)
+    DigGeom g;
+    // FSK
+    int32_t k, K, M, carry, nsym, new_carry;     // samples per symbol, transform size, tones, carried samples in / out, whole symbols
+    const uint32_t *map;      // [M] transform bin of each tone
+    const float2 *stash_rd;   // [carry] samples carried in
+    float2 *stash_wr;         // [new_carry] samples carried out
+};
+
+__host__ __device__ __forceinline__ uint32_t dig_gray_encode(uint32_t s) { return s ^ (s >> 1); }
+__host__ __device__ __forceinline__ uint32_t dig_gray_decode(uint32_t s) {
+    for (uint32_t k = s >> 1; k; k >>= 1) s ^= k;
+    return s;
+}
+
+// successive approximation over m bits with reference steps 2^k alpha (k = m-1 .. 0): the offset-binary level index; *res is what is left of v
+__host__ __device__ __forceinline__ uint32_t dig_linear(float v, int m, float alpha, float *res) {
+    uint32_t s = 0;
+    for (int k = m - 1; k >= 0; --k) {
+        const float ref = (float)(1u << k) * alpha;
+        s <<= 1;
+        if (v > 0.0f) { s |= 1u; v -= ref; }
+        else v += ref;
+    }
+    *res = v;
+    return s;
+}
+
+// amplitude level of an offset-binary index on a rail of 2^m levels: (2 s - 2^m + 1) alpha
+__host__ __device__ __forceinline__ float dig_level(uint32_t s, int m, float alpha) { return (float)(2 * (int)s - (1 << m) + 1) * alpha; }
+
+__host__ __device__ __forceinline__ float2 dig_unit(uint32_t s, float step) {
+    const float th = (float)s * step;
+    return make_float2(cosf(th), sinf(th));
+}
+
+// one sample's hard decision.  phi_prev: DPSK's phase of the previous input sample; *phi gets this sample's.  *xhat: the re-modulated decision.
+__host__ __device__ __forceinline__ uint32_t dig_decide(const DigGeom &g, float2 x, float phi_prev, float *phi, float2 *xhat) {
+    constexpr double kPi = 3.14159265358979323846;
+    float res;
+    switch (g.scheme) {
+    case DIG_PSK: {
+        float th = atan2f(x.y, x.x) - g.d_phi;
+        if (th < -kPi) th = (float)((double)th + 2.0 * kPi);
+        const uint32_t s = dig_linear(th, g.m_i, g.alpha, &res);
+        *xhat = dig_unit(s, g.step);
+        return dig_gray_encode(s);
+    }
+    case DIG_DPSK: {
+        const float th = atan2f(x.y, x.x);
+        float d = (th - phi_prev) - g.d_phi;
+        if (d > kPi) d = (float)((double)d - 2.0 * kPi);
+        else if (d < -kPi) d = (float)((double)d + 2.0 * kPi);
+        const uint32_t s = dig_linear(d, g.m_i, g.alpha, &res);
+        *phi = th;
+        const float t = th - res;
+        *xhat = make_float2(cosf(t), sinf(t));
+        return dig_gray_encode(s);
+    }
+    case DIG_ASK: {
+        const uint32_t s = dig_linear(x.x, g.m_i, g.alpha, &res);
+        *xhat = make_float2(dig_level(s, g.m_i, g.alpha), 0.0f);
+        return dig_gray_encode(s);
+    }
+    case DIG_QAM: {
+        const uint32_t si = dig_linear(x.x, g.m_i, g.alpha, &res), sq = dig_linear(x.y, g.m_q, g.alpha, &res);
+        *xhat = make_float2(dig_level(si, g.m_i, g.alpha), dig_level(sq, g.m_q, g.alpha));
+        return (dig_gray_encode(si) << g.m_q) | dig_gray_encode(sq);
+    }
+    case DIG_BPSK: {
+        const uint32_t s = x.x > 0.0f ? 0u : 1u;
+        *xhat = make_float2(s ? -1.0f : 1.0f, 0.0f);
+        return s;
+    }
+    case DIG_QPSK: {
+        const uint32_t s = (x.x > 0.0f ? 0u : 1u) | (x.y > 0.0f ? 0u : 2u);
+        const float h = 0.70710678118654752f;
+        *xhat = make_float2((s & 1u) ? -h : h, (s & 2u) ? -h : h);
+        return s;
+    }
+    default: {   // DIG_OOK: a mark at sqrt(2), a space at 0
+        const uint32_t s = x.x > 0.70710678118654752f ? 0u : 1u;
+        *xhat = make_float2(s ? 0.0f : 1.41421356237309505f, 0.0f);
+        return s;
+    }
+    }
+}
+
+__host__ __device__ __forceinline__ float dig_evm(float2 r, float2 xhat) {
+    const float dx = xhat.x - r.x, dy = xhat.y - r.y;
+    return sqrtf(dx * dx + dy * dy);
+}
+
+// FSK: the M tone bins of the K-point forward transform of one symbol's k samples (zero-padded to K), computed as M direct sums; the symbol is the
+// first tone of largest magnitude.  One wave per symbol: lane l sums the samples l, l + 64, ... for every tone, then the wave reduces.
+__device__ __forceinline__ uint32_t dig_fsk_symbol(const DigJob &j, int symbol, int lane) {
+    const int64_t p0 = (int64_t)symbol * j.k;
+    float best = 0.0f;
+    uint32_t arg = 0;
+    for (int t = 0; t < j.M; ++t) {
+        const uint32_t bin = j.map[t];
+        float re = 0.0f, im = 0.0f;
+        for (int n = lane; n < j.k; n += 64) {
+            const int64_t p = p0 + n;
+            const float2 x = p < j.carry ? j.stash_rd[p] : j.iq[p - j.carry];
+            const uint32_t e = (uint32_t)(((uint64_t)bin * (uint64_t)n) % (uint64_t)j.K);     // exp(-2 pi i bin n / K)
+            const float a = -6.28318530717958648f * ((float)e / (float)j.K);
+            const float s = sinf(a), c = cosf(a);
+            re += x.x * c - x.y * s;
+            im += x.x * s + x.y * c;
+        }
+        for (int o = 32; o > 0; o >>= 1) { re += __shfl_xor(re, o); im += __shfl_xor(im, o); }
+        const float v = sqrtf(re * re + im * im);
+        if (t == 0 || v > best) { best = v; arg = (uint32_t)t; }
+    }
+    return arg;
+}
+
+// grid (workgroups, jobs), kDigThreads threads.  Constellation job: workgroup x decides samples [x 256, + 256) -- one thread per sample, 8 B in,
+// 4 B out -- and workgroup 0 also writes the per-block EVM (the block's last sample, decided again by the thread that reports it; an empty block
+// repeats the state the object holds: the previous block's, or the one before the batch).  FSK job: wave w of workgroup x demodulates symbol
+// 4 x + w; workgroup 0 also moves the samples that do not fill a symbol into the carry stash.
+CSDR_KERNEL __launch_bounds__(kDigThreads) void digital_demod(const DigJob *__restrict__ jobs) {
+    const DigJob &j = jobs[blockIdx.y];
+    const int tid = threadIdx.x;
+    if (j.g.scheme == DIG_FSK) {
+        const int s = blockIdx.x * (kDigThreads / 64) + (tid >> 6), lane = tid & 63;
+        if (s < j.nsym) {
+            const uint32_t v = dig_fsk_symbol(j, s, lane);
+            if (lane == 0) j.sym[s] = v;
+        }
+        if (blockIdx.x == 0) {
+            const int64_t p0 = (int64_t)j.nsym * j.k;
+            for (int i = tid; i < j.new_carry; i += kDigThreads) {
+                const int64_t p = p0 + i;
+                j.stash_wr[i] = p < j.carry ? j.stash_rd[p] : j.iq[p - j.carry];
+            }
+        }
+        return;
+    }
+    const float2 r0 = make_float2(j.st_rd[0], j.st_rd[1]), xh0 = make_float2(j.st_rd[2], j.st_rd[3]);
+    const float phi0 = j.st_rd[4];
+    const int i = blockIdx.x * kDigThreads + tid;
+    if (i < j.n) {
+        const float2 x = j.iq[i];
+        const float prev = (j.g.scheme == DIG_DPSK && i > 0) ? atan2f(j.iq[i - 1].y, j.iq[i - 1].x) : phi0;
+        float phi = 0.0f;
+        float2 xh;
+        j.sym[i] = dig_decide(j.g, x, prev, &phi, &xh);
+        if (i == j.n - 1) {
+            j.st_wr[0] = x.x; j.st_wr[1] = x.y; j.st_wr[2] = xh.x; j.st_wr[3] = xh.y;
+            j.st_wr[4] = j.g.scheme == DIG_DPSK ? phi : phi0;
+        }
+    }
+    if (blockIdx.x == 0) {
+        for (int bb = tid; bb < j.nb; bb += kDigThreads) {
+            const int last = j.plan[bb + 1].j0 - 1;           // the last sample decided up to the end of this block
+            float e;
+            if (last < 0) e = dig_evm(r0, xh0);
+            else {
+                const float2 x = j.iq[last];
+                const float prev = (j.g.scheme == DIG_DPSK && last > 0) ? atan2f(j.iq[last - 1].y, j.iq[last - 1].x) : phi0;
+                float phi;
+                float2 xh;
+                (void)dig_decide(j.g, x, prev, &phi, &xh);
+                e = dig_evm(x, xh);
+            }
+            j.bevm[bb] = e;
+        }
+    }
+}
+
+}  // namespace csdr

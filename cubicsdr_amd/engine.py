@@ -211,6 +211,24 @@ class SDRPost:
             self.h = C.c_void_p()
 
 
+def digital_params(kind, cons=0, bps=0, sps=0, bw=0.0):
+    k = H.DIGITAL_BY_NAME[kind] if isinstance(kind, str) else int(kind)
+    return H.DigitalParams(k, int(cons), int(bps), int(sps), float(bw))
+
+
+def digital_run(ctx, kind, iq, sample_rate, state=None, cons=0, bps=0, sps=0, bw=0.0):
+    """csdr_digital_run: the decision kernel alone on `iq` (complex64) at the modem rate `sample_rate`, through one modem object whose state is
+    `state` (an H.DigitalState, updated in place; None = a fresh object).  Returns (symbols uint32, evm after the last sample, state)."""
+    d = digital_params(kind, cons, bps, sps, bw)
+    x = np.ascontiguousarray(iq, dtype=np.complex64)
+    st = state if state is not None else H.DigitalState()
+    out = np.empty(max(1, x.size + st.n_carry), np.uint32)
+    n, evm = C.c_int(), C.c_float()
+    H.check(H.lib().csdr_digital_run(ctx.h, C.byref(d), int(sample_rate), x.ctypes.data_as(C.c_void_p), int(x.size), C.byref(st),
+                                     out.ctypes.data_as(C.c_void_p), int(out.size), C.byref(n), C.byref(evm)))
+    return out[:n.value].copy(), evm.value, st
+
+
 class DemodBank:
     """N demodulator slots (csdr_bank); one slot = one DemodulatorInstance's Pre + Demod thread arithmetic."""
 
@@ -226,6 +244,29 @@ class DemodBank:
         m = H.MODEM_BY_NAME[modem] if isinstance(modem, str) else int(modem)
         p = H.DemodParams(m, int(bandwidth), int(audio_sample_rate), int(modem_arg), int(frequency))
         H.check(self._l.csdr_bank_configure_slot(self.h, int(slot), C.byref(p), post.h))
+
+    def configure_digital(self, slot, post, kind, bandwidth, frequency, cons=0, bps=0, sps=0, bw=0.0, audio_sample_rate=48000):
+        """a digital-lab modem (kind: "PSK", "DPSK", "ASK", "QAM", "BPSK", "QPSK", "OOK", "FSK" or CSDR_DIGITAL_*); 0 = the reference default"""
+        k = H.DIGITAL_BY_NAME[kind] if isinstance(kind, str) else int(kind)
+        p = H.DemodParams(H.CSDR_MODEM_DIGITAL, int(bandwidth), int(audio_sample_rate), 0, int(frequency))
+        d = digital_params(k, cons, bps, sps, bw)
+        H.check(self._l.csdr_bank_configure_digital_slot(self.h, int(slot), C.byref(p), C.byref(d), post.h))
+
+    def set_digital_cons(self, slot, cons):
+        """writeSetting("cons"): the next execute decides with constellation `cons`; every constellation keeps its own state"""
+        H.check(self._l.csdr_bank_set_digital_cons(self.h, int(slot), int(cons)))
+
+    def digital_results(self, slot):
+        arr = (H.DigitalResult * self.max_blocks)()
+        n = C.c_int()
+        H.check(self._l.csdr_bank_fetch_digital_results(self.h, int(slot), arr, self.max_blocks, C.byref(n)))
+        return [arr[i] for i in range(n.value)]
+
+    def symbols(self, slot, cap=1 << 22):
+        out = np.empty(cap, np.uint32)
+        n = C.c_int()
+        H.check(self._l.csdr_bank_fetch_symbols(self.h, int(slot), out.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+        return out[:n.value].copy()
 
     def set_frequency(self, slot, f):
         H.check(self._l.csdr_bank_set_frequency(self.h, int(slot), int(f)))

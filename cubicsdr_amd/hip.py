@@ -15,6 +15,10 @@ CSDR_POST_SINGLE, CSDR_POST_PFBCH, CSDR_POST_PFBCH2 = 0, 1, 2
 CSDR_MODEM_NBFM, CSDR_MODEM_FM, CSDR_MODEM_AM, CSDR_MODEM_USB, CSDR_MODEM_LSB, CSDR_MODEM_IQ, CSDR_MODEM_CW, CSDR_MODEM_DSB, CSDR_MODEM_FMS, CSDR_MODEM_HOST = range(10)
 CSDR_SPEC_FIRST_FRAME, CSDR_SPEC_CONTIGUOUS, CSDR_SPEC_LINES = 0, 1, 2
 MODEM_BY_NAME = {"NBFM": 0, "FM": 1, "AM": 2, "USB": 3, "LSB": 4, "I/Q": 5, "IQ": 5, "CW": 6, "DSB": 7, "FMS": 8, "HOST": 9}
+CSDR_MODEM_DIGITAL = 10
+CSDR_DIGITAL_PSK, CSDR_DIGITAL_DPSK, CSDR_DIGITAL_ASK, CSDR_DIGITAL_QAM, CSDR_DIGITAL_BPSK, CSDR_DIGITAL_QPSK, CSDR_DIGITAL_OOK, CSDR_DIGITAL_FSK = range(8)
+DIGITAL_BY_NAME = {"PSK": 0, "DPSK": 1, "ASK": 2, "QAM": 3, "BPSK": 4, "QPSK": 5, "OOK": 6, "FSK": 7}
+CSDR_DIGITAL_MAX_CARRY = 2048
 
 
 class DemodParams(C.Structure):
@@ -27,6 +31,21 @@ class BlockResult(C.Structure):
                 ("level_accum", C.c_double), ("level_count", C.c_int32), ("audio_peak", C.c_float),
                 ("nco_theta", C.c_uint32), ("resamp_phase", C.c_uint32), ("buffer_index", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class DigitalParams(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("cons", C.c_int32), ("bps", C.c_int32), ("sps", C.c_int32), ("bw", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+class DigitalResult(C.Structure):
+    _fields_ = [("n_symbols", C.c_int32), ("symbol_offset", C.c_int32), ("lock", C.c_int32), ("evm", C.c_float),
+                ("carry", C.c_int32), ("cons", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class DigitalState(C.Structure):
+    _fields_ = [("r", C.c_float * 2), ("x_hat", C.c_float * 2), ("phi", C.c_float), ("n_carry", C.c_int32),
+                ("reserved", C.c_int32 * 2), ("carry", C.c_float * (2 * CSDR_DIGITAL_MAX_CARRY))]
 
 
 class P2pOp(C.Structure):
@@ -168,6 +187,11 @@ ABI = {
     "csdr_comm_abort": (_i, [_p]),
     "csdr_comm_async_error": (_i, [_p]),
     "csdr_ingest_next_slot": (_i, [_p]),
+    "csdr_bank_configure_digital_slot": (_i, [_p, _i, C.POINTER(DemodParams), C.POINTER(DigitalParams), _p]),
+    "csdr_bank_set_digital_cons": (_i, [_p, _i, _i]),
+    "csdr_bank_fetch_digital_results": (_i, [_p, _i, C.POINTER(DigitalResult), _i, C.POINTER(_i)]),
+    "csdr_bank_fetch_symbols": (_i, [_p, _i, _p, _i, C.POINTER(_i)]),
+    "csdr_digital_run": (_i, [_p, C.POINTER(DigitalParams), _i64, _p, _i, C.POINTER(DigitalState), _p, _i, C.POINTER(_i), C.POINTER(_f)]),
 }
 
 _lib = None

@@ -26,6 +26,7 @@
 #include "DemodLevel.h"
 #include "IOThread.h"
 #include "Modem.h"
+#include "ModemDigital.h"
 #include "VisualProcessor.h"
 
 #define HEARTBEAT_CHECK_PERIOD_MICROS (50 * 1000)
@@ -86,6 +87,7 @@ public:
         std::lock_guard<std::mutex> g(mu_);
         if (kit_ && modem_) { modem_->disposeKit(kit_); kit_ = nullptr; }                   // DemodulatorThread.cpp:98-108
         type_ = t; bandwidth_ = Modem::getModemDefaultSampleRate(t); modem_ = std::move(m); dirty_ = true;
+        if (ModemDigital *md = dynamic_cast<ModemDigital *>(modem_.get())) md->setOutput(activeOutput_);   // DemodulatorInstance.cpp:318-333
         auto it = lastModemSettings_.find(t);
         if (it != lastModemSettings_.end()) modem_->writeSettings(it->second);
     }
@@ -138,6 +140,15 @@ public:
     void writeModemSettings(ModemSettings settings) { for (auto &kv : settings) writeModemSetting(kv.first, kv.second); }
     ModemSettings getLastModemSettings(const std::string &demodType) { std::lock_guard<std::mutex> g(mu_); return lastModemSettings_[demodType]; }
     int slot() const { return slot_; }
+    // digital lab (DemodulatorInstance.h:85-86,132): the modem's lock and its console output; 0 / no-op for other modems
+    void setDemodulatorLock(bool l) { std::lock_guard<std::mutex> g(mu_); if (ModemDigital *md = dynamic_cast<ModemDigital *>(modem_.get())) md->setDemodulatorLock(l); }
+    int getDemodulatorLock() { std::lock_guard<std::mutex> g(mu_); ModemDigital *md = dynamic_cast<ModemDigital *>(modem_.get()); return md ? md->getDemodulatorLock() : 0; }
+    void setOutput(ModemDigitalOutput *out) {
+        std::lock_guard<std::mutex> g(mu_);
+        activeOutput_ = out;
+        if (ModemDigital *md = dynamic_cast<ModemDigital *>(modem_.get())) md->setOutput(out);
+    }
+    ModemDigitalOutput *getOutput() { std::lock_guard<std::mutex> g(mu_); return activeOutput_; }
 
 private:
     friend class SDRPostThread;
@@ -155,6 +166,8 @@ private:
     std::atomic_bool active_{false}, terminated_{false}, squelchEnabled_{false}, muted_{false};
     std::atomic<float> squelchLevel_{-100.0f}, signalLevel_{-100.0f}, signalFloor_{-30.0f}, signalCeil_{30.0f}, gain_{1.0f};
     bool squelchBreak_ = false;
+    ModemDigitalOutput *activeOutput_ = nullptr;
+    int appliedCons_ = 0;                     // digital modems: the constellation the bank slot decides with
     AudioThreadInputQueuePtr audioQueue_;
     DemodulatorThreadInputQueuePtr pipeIQInputData_;
     DemodulatorThreadOutputQueuePtr audioVisQueue_;
@@ -290,22 +303,31 @@ private:
             d->setActive(inRange);
             bool rebuild;
             csdr_demod_params p{};
+            csdr_digital_params dp{};
+            int newCons = 0;
             {
                 std::lock_guard<std::mutex> g(d->mu_);
                 rebuild = d->dirty_ || d->builtRate_ != chanRate;
                 p.modem = d->modem_ ? d->modem_->csdrModemId() : -1; p.bandwidth = d->bandwidth_; p.audio_sample_rate = d->audioRate_;
                 p.modem_arg = d->modem_ ? d->modem_->csdrModemArg() : 0;
                 p.frequency = d->getFrequency();
+                if (ModemDigital *md = dynamic_cast<ModemDigital *>(d->modem_.get())) { dp = md->csdrDigitalParams(); newCons = md->csdrDigitalCons(); }
                 if (rebuild && inRange) {
                     d->dirty_ = false; d->builtRate_ = chanRate;
-                    if (d->modem_ && p.modem == CSDR_MODEM_HOST) {                  // DemodulatorWorkerThread.cpp:63-76: a fresh kit per (re)build
+                    if (d->modem_ && (p.modem == CSDR_MODEM_HOST || p.modem == CSDR_MODEM_DIGITAL)) {   // DemodulatorWorkerThread.cpp:63-76: a fresh kit per (re)build
                         if (d->kit_) d->modem_->disposeKit(d->kit_);
                         d->kit_ = d->modem_->buildKit(d->bandwidth_, d->audioRate_);
                     }
                 }
             }
             if (!inRange) { (void)csdr_bank_set_active(bank_, d->slot(), 0); continue; }
-            if (rebuild) CSDR_STAGE_TRY(csdr_bank_configure_slot(bank_, d->slot(), &p, post_), "csdr_bank_configure_slot");
+            if (p.modem == CSDR_MODEM_DIGITAL) {
+                if (rebuild) { CSDR_STAGE_TRY(csdr_bank_configure_digital_slot(bank_, d->slot(), &p, &dp, post_), "csdr_bank_configure_digital_slot"); d->appliedCons_ = dp.cons; }
+                else if (newCons && newCons != d->appliedCons_) {          // writeSetting("cons"): updateDemodulatorCons, no rebuild
+                    CSDR_STAGE_TRY(csdr_bank_set_digital_cons(bank_, d->slot(), newCons), "csdr_bank_set_digital_cons");
+                    d->appliedCons_ = newCons;
+                }
+            } else if (rebuild) CSDR_STAGE_TRY(csdr_bank_configure_slot(bank_, d->slot(), &p, post_), "csdr_bank_configure_slot");
             CSDR_STAGE_TRY(csdr_bank_set_frequency(bank_, d->slot(), d->getFrequency()), "csdr_bank_set_frequency");
             CSDR_STAGE_TRY(csdr_bank_set_active(bank_, d->slot(), 1), "csdr_bank_set_active");
             run.push_back(d);
@@ -345,6 +367,9 @@ private:
         int nb = 0;
         CSDR_STAGE_TRY(csdr_bank_fetch_results(bank_, d.slot(), &r, 1, &nb), "csdr_bank_fetch_results");
         if (nb != 1 || r.skipped || r.n_iq == 0) return;
+        bool digital;
+        { std::lock_guard<std::mutex> g(d.mu_); digital = dynamic_cast<ModemDigital *>(d.modem_.get()) != nullptr; }
+        if (digital) { finishDigital(d, r); return; }
         AudioThreadInputPtr ati = d.outputBuffers_.getBuffer();
         ati->sampleRate = d.getAudioSampleRate(); ati->inputRate = d.getBandwidth(); ati->channels = (d.getDemodulatorType() == "I/Q" || d.getDemodulatorType() == "FMS") ? 2 : 1; ati->frequency = d.getFrequency();
         int got = 0;
@@ -439,6 +464,62 @@ private:
             if (mixSource) { mixSlots_.push_back(d.slot()); mixSources_.push_back(mixSource); }      // HBM -> the mixer's ring, after the loop
             else (void)d.audioQueue_->try_push(ati);                                   // never blocks (:322)
         }
+    }
+
+    // DemodulatorThread::run for a digital modem (:115-140, :245-267, :318-328): the modem's lock after the block (updateDemodulatorLock; FSK never
+    // updates it), FSK's hex text to the output (digitalFinish), an AudioThreadInput at the kit's rate with no audio -- so the level step sees no
+    // signal -- and, when the scope queue is bound and empty, the block's IQ as a constellation frame instead of the audio
+    void finishDigital(DemodulatorInstance &d, const csdr_block_result &r) {
+        csdr_digital_result dr;
+        int nb = 0;
+        CSDR_STAGE_TRY(csdr_bank_fetch_digital_results(bank_, d.slot(), &dr, 1, &nb), "csdr_bank_fetch_digital_results");
+        if (nb != 1) return;
+        ModemDigital *md;
+        long long kitRate;
+        int bandwidth;
+        bool fsk;
+        DemodulatorThreadOutputQueuePtr vis;
+        {
+            std::lock_guard<std::mutex> g(d.mu_);
+            md = dynamic_cast<ModemDigital *>(d.modem_.get());
+            if (!md) return;
+            bandwidth = d.bandwidth_;
+            kitRate = d.kit_ ? d.kit_->sampleRate : bandwidth;
+            fsk = md->csdrDigitalParams().kind == CSDR_DIGITAL_FSK;
+            vis = d.audioVisQueue_;
+            if (!fsk) md->setDemodulatorLock(dr.lock != 0);
+        }
+        if (fsk && dr.n_symbols > 0) {
+            std::vector<uint32_t> sym((size_t)dr.n_symbols);
+            int got = 0;
+            CSDR_STAGE_TRY(csdr_bank_fetch_symbols(bank_, d.slot(), sym.data(), dr.n_symbols, &got), "csdr_bank_fetch_symbols");
+            md->digitalFinish(ModemFSK::hexText(sym.data(), got));
+        }
+        AudioThreadInputPtr ati = d.outputBuffers_.getBuffer();
+        ati->sampleRate = (int)kitRate; ati->inputRate = bandwidth; ati->channels = 1; ati->frequency = d.getFrequency();
+        ati->data.resize(0);
+        const double sampleTime = double(r.n_iq) / double(bandwidth);
+        DemodLevelState st;
+        st.signalLevel = d.signalLevel_; st.signalFloor = d.signalFloor_; st.signalCeil = d.signalCeil_; st.squelchBreak = d.squelchBreak_;
+        const bool squelched = demodLevelStep(st, false, 0.0, 0, sampleTime, d.squelchEnabled_, d.squelchLevel_);
+        d.signalLevel_ = st.signalLevel; d.signalFloor_ = st.signalFloor; d.signalCeil_ = st.signalCeil; d.squelchBreak_ = st.squelchBreak;
+        ati->peak = 0.0f;
+        ati->is_squelch_active = squelched;
+        bool tapped = false;
+        if (!squelched && vis && vis->empty()) {                                               // :256-267
+            std::vector<liquid_float_complex_t> iq((size_t)r.n_iq);
+            int got = 0;
+            CSDR_STAGE_TRY(csdr_bank_fetch_iq(bank_, d.slot(), (float *)iq.data(), r.n_iq, &got), "csdr_bank_fetch_iq");
+            AudioThreadInputPtr ati_vis = std::make_shared<AudioThreadInput>();
+            ati_vis->sampleRate = bandwidth; ati_vis->inputRate = bandwidth;
+            ati_vis->data.resize((size_t)got);                                   // inputData->size() floats: the first size / 2 samples, interleaved
+            for (int i = 0; i < got / 2; i++) { ati_vis->data[2 * i] = iq[i].real; ati_vis->data[2 * i + 1] = iq[i].imag; }
+            ati_vis->channels = 2;
+            ati_vis->type = 2;
+            (void)vis->try_push(ati_vis);
+            tapped = true;                                                       // the reference drops the block's (empty) audio then
+        }
+        if (!tapped && !squelched && !d.muted_) (void)d.audioQueue_->try_push(ati);
     }
 
     csdr_ctx *ctx_;

@@ -105,6 +105,7 @@ public:
     virtual int csdrModemArg() { return 0; }
 
     static void registerBuiltins();
+    static void registerDigitalLab();        // ModemDigital.h: the digital lab's modems (the reference's ENABLE_DIGITAL_LAB), opt-in
 
 private:
     static ModemFactoryList &factories() { static ModemFactoryList f; return f; }

@@ -1,0 +1,190 @@
+// ModemDigital.h -- the reference's digital lab (src/modules/modem/ModemDigital.{h,cpp}, src/modules/modem/digital/*.cpp, built there with
+// ENABLE_DIGITAL_LAB) over the HIP library.  As for the analog modems, the objects are host-side DESCRIPTORS: name / type, settings, rates and the
+// csdr_digital_params of the bank slot; the decisions run on the device (csdr_bank_execute).  What the reference keeps in the modem
+// object and the application reads back -- the lock (ModemDigital.cpp:43-53) and the console output (ModemDigitalOutput) -- stays here:
+// SDRPostThread::finishDemod sets the lock from the block's csdr_digital_result and hands FSK's text to the output.
+// Registration is opt-in like the reference's build switch: Modem::registerDigitalLab().  APSK, SQAM, ST (V.29) and GMSK are not built
+// (DESIGN 9); they remain available as host plug-ins through Modem::addModemFactory.
+#pragma once
+#include <atomic>
+#include <cmath>
+#include <cstdio>
+#include <mutex>
+#include <stdexcept>
+#include <string>
+
+#include "Modem.h"
+
+class ModemKitDigital : public ModemKit {                    // ModemDigital.h:9-13
+public:
+    ModemKitDigital() = default;
+};
+
+class ModemDigitalOutput {                                   // ModemDigital.h:15-27: where a digital modem writes its console text
+public:
+    ModemDigitalOutput() = default;
+    virtual ~ModemDigitalOutput() = default;
+    virtual void write(std::string outp) = 0;
+    virtual void write(char outc) = 0;
+    virtual void Show() = 0;
+    virtual void Hide() = 0;
+    virtual void Close() = 0;
+};
+
+class ModemDigital : public Modem {                          // ModemDigital.h:29-60
+public:
+    ModemDigital() = default;
+    std::string getType() override { return "digital"; }
+    int checkSampleRate(long long sampleRate, int /* audioSampleRate */) override {    // ModemDigital.cpp:21-26
+        return sampleRate < MIN_BANDWIDTH ? MIN_BANDWIDTH : (int)sampleRate;
+    }
+    ModemKit *buildKit(long long sampleRate, int audioSampleRate) override {          // ModemDigital.cpp:28-35
+        ModemKitDigital *k = new ModemKitDigital;
+        k->sampleRate = sampleRate; k->audioSampleRate = audioSampleRate;
+        return k;
+    }
+    void disposeKit(ModemKit *kit) override { delete kit; }
+    void setDemodulatorLock(bool demod_lock_in) { currentDemodLock.store(demod_lock_in); }
+    int getDemodulatorLock() { return currentDemodLock.load(); }
+    void setOutput(ModemDigitalOutput *modemDigitalOutput) { std::lock_guard<std::mutex> g(outMu_); digitalOut = modemDigitalOutput; }
+    ModemDigitalOutput *getOutput() { std::lock_guard<std::mutex> g(outMu_); return digitalOut; }
+    // digitalFinish (ModemDigital.cpp:65-76): the block's console text to the output, when there is any and an output is set
+    void digitalFinish(const std::string &text) {
+        std::lock_guard<std::mutex> g(outMu_);
+        if (digitalOut && !text.empty()) digitalOut->write(text);
+    }
+    // the decisions run on the device: nothing may route a block through the host entry
+    void demodulate(ModemKit *, ModemIQData *, AudioThreadInput *) override {
+        throw std::logic_error("ModemDigital::demodulate: this modem's decisions run on the device (csdr_bank_execute)");
+    }
+    int csdrModemId() override { return CSDR_MODEM_DIGITAL; }
+    // the slot's settings (csdr_bank_configure_digital_slot)
+    virtual csdr_digital_params csdrDigitalParams() = 0;
+    // the constellation the device should decide with now (writeSetting("cons") needs no rebuild: csdr_bank_set_digital_cons); 0 = none
+    virtual int csdrDigitalCons() { return 0; }
+
+protected:
+    std::atomic_bool currentDemodLock{false};
+
+private:
+    std::mutex outMu_;
+    ModemDigitalOutput *digitalOut = nullptr;
+};
+
+// ModemPSK / ModemDPSK / ModemASK / ModemQAM: the "cons" setting (ModemPSK.cpp:39-94 and alike); a write switches the constellation without a rebuild
+template <int KIND>
+class ModemDigitalCons : public ModemDigital {
+public:
+    static ModemBase *factory() { return new ModemDigitalCons<KIND>(); }
+    std::string getName() override {
+        switch (KIND) { case CSDR_DIGITAL_PSK: return "PSK"; case CSDR_DIGITAL_DPSK: return "DPSK"; case CSDR_DIGITAL_ASK: return "ASK"; }
+        return "QAM";
+    }
+    ModemArgInfoList getSettings() override {
+        ModemArgInfo a;
+        a.key = "cons"; a.name = "Constellation"; a.description = "Modem Constellation Pattern"; a.value = std::to_string(cons_.load());
+        for (int c = KIND == CSDR_DIGITAL_QAM ? 4 : 2; c <= 256; c *= 2) a.options.push_back(std::to_string(c));
+        return ModemArgInfoList{a};
+    }
+    void writeSetting(std::string setting, std::string value) override {
+        if (setting != "cons") return;
+        const int c = std::stoi(value);
+        // updateDemodulatorCons: a value outside the options leaves the object in use (its switch has no default); cons records it anyway
+        bool known = false;
+        for (int v = KIND == CSDR_DIGITAL_QAM ? 4 : 2; v <= 256; v *= 2) known = known || v == c;
+        shownCons_.store(c);
+        if (known) cons_.store(c);
+    }
+    std::string readSetting(std::string setting) override { return setting == "cons" ? std::to_string(shownCons_.load()) : ""; }
+    csdr_digital_params csdrDigitalParams() override { csdr_digital_params p{}; p.kind = KIND; p.cons = cons_.load(); return p; }
+    int csdrDigitalCons() override { return cons_.load(); }
+
+private:
+    std::atomic<int> cons_{KIND == CSDR_DIGITAL_QAM ? 4 : 2}, shownCons_{KIND == CSDR_DIGITAL_QAM ? 4 : 2};
+};
+
+// ModemBPSK / ModemQPSK / ModemOOK: no settings
+template <int KIND>
+class ModemDigitalFixed : public ModemDigital {
+public:
+    static ModemBase *factory() { return new ModemDigitalFixed<KIND>(); }
+    std::string getName() override { return KIND == CSDR_DIGITAL_BPSK ? "BPSK" : (KIND == CSDR_DIGITAL_QPSK ? "QPSK" : "OOK"); }
+    csdr_digital_params csdrDigitalParams() override { csdr_digital_params p{}; p.kind = KIND; return p; }
+};
+
+typedef ModemDigitalCons<CSDR_DIGITAL_PSK> ModemPSK;
+typedef ModemDigitalCons<CSDR_DIGITAL_DPSK> ModemDPSK;
+typedef ModemDigitalCons<CSDR_DIGITAL_ASK> ModemASK;
+typedef ModemDigitalCons<CSDR_DIGITAL_QAM> ModemQAM;
+typedef ModemDigitalFixed<CSDR_DIGITAL_BPSK> ModemBPSK;
+typedef ModemDigitalFixed<CSDR_DIGITAL_QPSK> ModemQPSK;
+typedef ModemDigitalFixed<CSDR_DIGITAL_OOK> ModemOOK;
+
+// ModemFSK (ModemFSK.cpp): bps / sps / bw, each write asks for a rebuild; the symbols go to the output as lowercase hex
+class ModemFSK : public ModemDigital {
+public:
+    static ModemBase *factory() { return new ModemFSK(); }
+    std::string getName() override { return "FSK"; }
+    int getDefaultSampleRate() override { return 19200; }
+    int checkSampleRate(long long sampleRate, int /* audioSampleRate */) override {    // ModemFSK.cpp:19-28
+        const double minSps = std::pow(2.0, bps_.load());
+        const double nextSps = double(sampleRate) / double(sps_.load());
+        return nextSps < minSps ? 2 * bps_.load() * sps_.load() : (int)sampleRate;
+    }
+    ModemArgInfoList getSettings() override {                                          // ModemFSK.cpp:34-76
+        ModemArgInfoList args;
+        ModemArgInfo b;
+        b.key = "bps"; b.name = "Bits/symbol"; b.value = std::to_string(bps_.load()); b.description = "Modem bits-per-symbol"; b.units = "bits";
+        b.options = {"1", "2", "4", "8", "16"};
+        args.push_back(b);
+        ModemArgInfo s;
+        s.key = "sps"; s.name = "Symbols/second"; s.value = std::to_string(sps_.load()); s.description = "Modem symbols-per-second";
+        args.push_back(s);
+        ModemArgInfo w;
+        w.key = "bw"; w.name = "Signal bandwidth"; w.value = std::to_string(bw_.load()); w.description = "Total signal bandwidth";
+        args.push_back(w);
+        return args;
+    }
+    void writeSetting(std::string setting, std::string value) override {               // ModemFSK.cpp:78-90
+        if (setting == "bps") { bps_.store(std::stoi(value)); rebuildKit(); }
+        else if (setting == "sps") { sps_.store(std::stoi(value)); rebuildKit(); }
+        else if (setting == "bw") { bw_.store(std::stof(value)); rebuildKit(); }
+    }
+    std::string readSetting(std::string setting) override {
+        if (setting == "bps") return std::to_string(bps_.load());
+        if (setting == "sps") return std::to_string(sps_.load());
+        if (setting == "bw") return std::to_string(bw_.load());
+        return "";
+    }
+    csdr_digital_params csdrDigitalParams() override {
+        csdr_digital_params p{};
+        p.kind = CSDR_DIGITAL_FSK; p.bps = bps_.load(); p.sps = sps_.load(); p.bw = bw_.load();
+        return p;
+    }
+    // outStream << std::hex << symbol (ModemFSK.cpp:12, :137)
+    static std::string hexText(const uint32_t *sym, int n) {
+        std::string s;
+        char buf[16];
+        for (int i = 0; i < n; ++i) { snprintf(buf, sizeof buf, "%x", sym[i]); s += buf; }
+        return s;
+    }
+
+private:
+    std::atomic<int> bps_{1}, sps_{9600};                                                 // ModemFSK.cpp:7-12
+    std::atomic<float> bw_{0.45f};
+};
+
+inline void Modem::registerDigitalLab() {                                               // CubicSDR.cpp:315-328 (the built ones)
+    registerBuiltins();
+    static std::once_flag once;
+    std::call_once(once, [] {
+    addModemFactory(ModemASK::factory, "ASK", 200000);
+    addModemFactory(ModemBPSK::factory, "BPSK", 200000);
+    addModemFactory(ModemDPSK::factory, "DPSK", 200000);
+    addModemFactory(ModemFSK::factory, "FSK", 19200);
+    addModemFactory(ModemOOK::factory, "OOK", 200000);
+    addModemFactory(ModemPSK::factory, "PSK", 200000);
+    addModemFactory(ModemQAM::factory, "QAM", 200000);
+    addModemFactory(ModemQPSK::factory, "QPSK", 200000);
+    });
+}

@@ -224,6 +224,70 @@ int  csdr_bank_fetch_fms_stage(csdr_bank *bank, int slot, int which, void *host_
 /* device-side total of audio samples produced by the last execute over all slots (bench sanity) */
 int  csdr_bank_total_audio(csdr_bank *bank, int64_t *n);
 
+/* ------------------------------------------------------------------ digital lab (src/modules/modem/digital/, ENABLE_DIGITAL_LAB)
+ * A digital slot runs DemodulatorPreThread's arithmetic (NCO shift + msresamp_crcf to the modem rate, as any slot) and then the modem's
+ * hard decisions: one per resampled IQ sample for the modemcf constellations (ModemPSK.cpp:108-118 and alike: no symbol timing), one per
+ * k = rate / sps samples for FSK (ModemFSK.cpp:127-143, the samples short of a symbol carried to the next block).  No audio: n_audio, level
+ * and peak of its csdr_block_result stay 0.  Not built: APSK, SQAM, V.29 (ModemST) and GMSK. */
+#define CSDR_MODEM_DIGITAL 10        /* configured only through csdr_bank_configure_digital_slot */
+#define CSDR_DIGITAL_PSK   0         /* ModemPSK   modemcf PSK2..PSK256, lock at EVM <= 0.005 */
+#define CSDR_DIGITAL_DPSK  1         /* ModemDPSK  modemcf DPSK2..DPSK256, 0.005 */
+#define CSDR_DIGITAL_ASK   2         /* ModemASK   modemcf ASK2..ASK256, 0.005 */
+#define CSDR_DIGITAL_QAM   3         /* ModemQAM   modemcf QAM4..QAM256 (square and rectangular), 0.5 */
+#define CSDR_DIGITAL_BPSK  4         /* ModemBPSK, 0.005 */
+#define CSDR_DIGITAL_QPSK  5         /* ModemQPSK, 0.8 */
+#define CSDR_DIGITAL_OOK   6         /* ModemOOK, 0.005 */
+#define CSDR_DIGITAL_FSK   7         /* ModemFSK   fskdem(bps, rate / sps, bw); no lock (the reference never updates it) */
+
+typedef struct csdr_digital_params {
+    int32_t kind;              /* CSDR_DIGITAL_* (the reference class) */
+    int32_t cons;              /* PSK / DPSK / ASK: 2..256, QAM: 4..256, a power of two ("cons" setting); 0 = the reference default (2; QAM 4) */
+    int32_t bps;               /* FSK bits per symbol ("bps"; 0 = 1) */
+    int32_t sps;               /* FSK symbols per second ("sps"; 0 = 9600) */
+    float   bw;                /* FSK signal bandwidth as a fraction of the modem rate ("bw"; 0 = 0.45) */
+    int32_t reserved[3];       /* 0 */
+} csdr_digital_params;
+
+/* per (digital slot, block) of the last execute */
+typedef struct csdr_digital_result {
+    int32_t n_symbols;         /* decisions of this block */
+    int32_t symbol_offset;     /* where they start in csdr_bank_fetch_symbols' output */
+    int32_t lock;              /* updateDemodulatorLock after the block (ModemDigital.cpp:51-53): evm <= the modem's sensitivity; FSK: 0 */
+    float   evm;               /* modemcf_get_demodulator_evm after the block: |x_hat - r| of the last decided sample (a block without samples
+                                  repeats the previous value); FSK: 0 */
+    int32_t carry;             /* FSK: samples held for the next symbol after the block (kit->inputBuffer.size()); else 0 */
+    int32_t cons;              /* the constellation size the block was decided with (FSK: 2^bps; BPSK / QPSK / OOK: 2, 4, 2) */
+    int32_t reserved[2];
+} csdr_digital_result;
+
+/* state of one modem object for csdr_digital_run (zero = freshly created) */
+#define CSDR_DIGITAL_MAX_CARRY 2048
+typedef struct csdr_digital_state {
+    float   r[2], x_hat[2];    /* last demodulated sample and its re-modulated decision (what the EVM compares) */
+    float   phi;               /* DPSK: phase of the previous input sample */
+    int32_t n_carry;           /* FSK: samples carried (< k) */
+    int32_t reserved[2];
+    float   carry[2 * CSDR_DIGITAL_MAX_CARRY];   /* FSK: the carried samples, interleaved complex */
+} csdr_digital_state;
+
+/* (Re)build slot `slot` as a digital modem: p->modem must be CSDR_MODEM_DIGITAL; p->bandwidth is the modem rate before checkSampleRate
+ * (ModemDigital.cpp:21-26: at least 500 Hz; ModemFSK.cpp:19-28).  Every constellation of the kind starts fresh.  CSDR_EUNSUPPORTED for settings
+ * the reference cannot build: a cons outside its list, FSK with k = rate / sps outside [2, 2048] or bw outside (0, 0.5) (fskdem_create returns
+ * no object), or tones that share a transform bin (fskdem_create reports that and goes on; bps above 16 always does). */
+int  csdr_bank_configure_digital_slot(csdr_bank *bank, int slot, const csdr_demod_params *p, const csdr_digital_params *d, const csdr_post *post);
+/* writeSetting("cons") (updateDemodulatorCons): switch to constellation `cons` from the next execute on.  The front-end is not reset, and every
+ * constellation keeps its own state (ModemPSK and alike create all of them up front): switching back resumes where that one stopped. */
+int  csdr_bank_set_digital_cons(csdr_bank *bank, int slot, int cons);
+/* per-block results of the last execute (synchronises) */
+int  csdr_bank_fetch_digital_results(csdr_bank *bank, int slot, csdr_digital_result *out, int cap_blocks, int *n_blocks);
+/* the symbols of the last execute, all blocks in order (synchronises) */
+int  csdr_bank_fetch_symbols(csdr_bank *bank, int slot, uint32_t *host_out, int cap, int *n);
+/* The decision kernel alone on n caller-supplied samples at the modem rate `sample_rate` (FSK: k = sample_rate / sps), one modem object whose
+ * state is *state (read, then updated); for parity checks on identical input.  Symbols go to sym_host (*n_symbols of them: n for a
+ * constellation, whole symbols for FSK), *evm_last is the object's EVM afterwards (FSK: 0). */
+int  csdr_digital_run(csdr_ctx *ctx, const csdr_digital_params *d, int64_t sample_rate, const float *iq_host, int n, csdr_digital_state *state,
+                      uint32_t *sym_host, int cap_symbols, int *n_symbols, float *evm_last);
+
 /* ------------------------------------------------------------------ SpectrumVisualProcessor (src/process/SpectrumVisualProcessor.cpp)
  * replaces: setup :140-178 (fft_create_plan(2*fftSize, FORWARD)), process :212-637 full-span view:
  * frame selection :387-421, fft_execute :439, magnitude + fftshift :441-452, double EMA + min/max :494-530,
