@@ -1,11 +1,13 @@
 // csdr_digital.hip -- the digital lab (reference src/modules/modem/digital/): configuration of digital slots, their per-batch plan and launch behind
-// the bank's front-end, the result fetches, and csdr_digital_run (the decision kernel alone).  Kernel: kernels_digital.hpp; DESIGN 15.
+// the bank's front-end, the result fetches, csdr_digital_run (the decision kernel alone) and csdr_gmsk_run (the GMSK kernels alone).  Kernels:
+// kernels_digital.hpp; DESIGN 15.
 #include <algorithm>
 #include <cmath>
 #include <memory>
 #include <vector>
 
 #include "csdr_objects.hpp"
+#include "design.hpp"
 #include "kernels_digital.hpp"
 
 using namespace csdr;
@@ -22,7 +24,8 @@ struct DigSlot {
     int k = 0, K = 0, M = 0;                 // FSK: samples per symbol, transform size, tones
     int carry = 0, stash_cur = 0;            // FSK: samples held (kit->inputBuffer), which stash copy holds them
     int st_cur[kDigRecords] = {0};           // which copy of each constellation's state is current
-    void *mem = nullptr;                     // device: sym [cap_sym] | bevm [max_blocks] | st [8][2][8] | stash [2][kDigFskMaxK] | map [M]
+    void *mem = nullptr;                     // device: sym [cap_sym] | bevm [max_blocks] | st [8][2][8] | stash [2][kDigFskMaxK] | map [M]; GMSK: sym [cap_sym] |
+                                             // taps | history | plan | phase differences, nothing of the others
     uint32_t *sym = nullptr;
     float *bevm = nullptr, *st = nullptr;
     float2 *stash = nullptr;
@@ -35,6 +38,15 @@ struct DigSlot {
     int run_idx = 0, run_cons = 0;
     // planned by bank_digital_plan, launched by bank_digital_launch
     int n = 0, new_carry = 0, nsym_plan = 0;
+    // GMSK: gmskdem(gk = sps, gm = fdelay, BT = bw), gL = 2 gk gm + 1 taps
+    int gk = 0, gm = 0, gL = 0, hist_cur = 0;
+    int64_t gcarry = 0;                      // kit->inputBuffer.size() (only its count is ever used) before the batch ...
+    int64_t gcarry_new = 0;                  // ... and after it: planned, committed when the batch launches (a rejected batch changes nothing)
+    float *gh = nullptr, *ghist = nullptr;   // device (inside mem): taps [gL] | history [2][gL + 1] (gL - 1 phase differences, x_prime)
+    GmskBlock *gblk_d = nullptr;             // device: the batch's plan [max_blocks + 1]
+    float *gphi = nullptr;                   // device: the batch's phase-difference stream [cap_phi]
+    int64_t cap_phi = 0;
+    std::vector<GmskBlock> gblk;             // the batch's plan [NB + 1]
     ~DigSlot() { if (mem) (void)hipFree(mem); }
 };
 
@@ -46,7 +58,19 @@ static int ilog2(int v) { int m = 0; while ((1 << m) < v) ++m; return m; }
 // defaults of the reference constructors (ModemPSK.cpp:6-15 cons = 2, ModemQAM cons = 4, ModemFSK.cpp:7-12 bps 1, sps 9600, bw 0.45)
 static int dig_normalise(const csdr_digital_params *in, csdr_digital_params *out) {
     *out = *in;
-    if (in->kind < CSDR_DIGITAL_PSK || in->kind > CSDR_DIGITAL_FSK) return fail(CSDR_EINVAL, "digital kind %d", in->kind);
+    if (in->kind < CSDR_DIGITAL_PSK || in->kind > CSDR_DIGITAL_GMSK) return fail(CSDR_EINVAL, "digital kind %d", in->kind);
+    if (in->kind == CSDR_DIGITAL_GMSK) {      // ModemGMSK.cpp:7-10: sps 4, fdelay 3, ebf 0.3
+        if (!out->sps) out->sps = 4;
+        if (!out->fdelay) out->fdelay = 3;
+        if (out->bw == 0.0f) out->bw = 0.3f;
+        out->cons = 0; out->bps = 0;
+        // gmskdem_create returns no object for k < 2, m < 1 or BT outside (0, 1); beyond the settings' ranges (sps 2..512, fdelay 1..128) the
+        // filter length is walled off
+        if (out->sps < 2 || out->fdelay < 1 || !(out->bw > 0.0f && out->bw < 1.0f))
+            return fail(CSDR_EUNSUPPORTED, "GMSK sps %d / fdelay %d / ebf %g: gmskdem_create builds no demodulator", out->sps, out->fdelay, (double)out->bw);
+        if (out->sps > 512 || out->fdelay > 128) return fail(CSDR_EUNSUPPORTED, "GMSK sps %d / fdelay %d beyond the settings' ranges (512, 128)", out->sps, out->fdelay);
+        return CSDR_OK;
+    }
     if (in->kind == CSDR_DIGITAL_FSK) {
         if (!out->bps) out->bps = 1;
         if (!out->sps) out->sps = 9600;
@@ -109,6 +133,7 @@ static int dig_geometry(const csdr_digital_params &p, DigGeom *g, int *idx, floa
     case CSDR_DIGITAL_BPSK: g->scheme = DIG_BPSK; break;
     case CSDR_DIGITAL_QPSK: g->scheme = DIG_QPSK; *sens = 0.8f; break;
     case CSDR_DIGITAL_OOK: g->scheme = DIG_OOK; break;
+    case CSDR_DIGITAL_GMSK: g->scheme = DIG_GMSK; *sens = -1.0f; break;
     default: g->scheme = DIG_FSK; *sens = -1.0f; break;
     }
     return CSDR_OK;
@@ -160,10 +185,11 @@ static int dig_setup(const csdr_digital_params *in, int64_t rate, DigSlot *d, st
         if (int rc = dig_fsk_plan(d->p.bps, (int)k, d->p.bw, &d->K, map)) return rc;
         d->k = (int)k; d->M = 1 << d->p.bps;
     }
+    if (d->p.kind == CSDR_DIGITAL_GMSK) { d->gk = d->p.sps; d->gm = d->p.fdelay; d->gL = 2 * d->gk * d->gm + 1; }
     return CSDR_OK;
 }
 
-static int dig_cons_of(const DigSlot &d) { return d.p.kind == CSDR_DIGITAL_FSK ? d.M : d.p.cons; }
+static int dig_cons_of(const DigSlot &d) { return d.p.kind == CSDR_DIGITAL_FSK ? d.M : d.p.kind == CSDR_DIGITAL_GMSK ? 2 : d.p.cons; }
 
 extern "C" int csdr_bank_configure_digital_slot(csdr_bank *b, int slot, const csdr_demod_params *p, const csdr_digital_params *dp, const csdr_post *post) {
     DeviceScope dev__(b ? b->ctx : nullptr);
@@ -182,18 +208,36 @@ extern "C" int csdr_bank_configure_digital_slot(csdr_bank *b, int slot, const cs
     q.bandwidth = (int32_t)rate;
     if (int rc = bank_configure_slot(b, slot, &q, post)) return rc;      // (resets the slot, its digital stage included)
     SlotHost &s = b->slots[slot];
+    const bool gmsk = d->gL > 0;
     d->cap_sym = s.cfg.cap_iq;
+    if (gmsk) {
+        // ModemGMSK's count c stays at or below n_max (k - 1) + k for blocks of at most n_max samples (c' = S - k ceil(floor(S / k) / k) <=
+        // S (k - 1) / k + 1 with S = c + n), and a batch reads c_before + (its samples) - c_after of them: the stream and the decisions of any
+        // batch fit these sizes, fixed here once
+        const int64_t k = d->gk, n_max = (s.cfg.cap_iq - 64 - b->max_blocks) / std::max(1, b->max_blocks) + 2;
+        const int64_t reads = n_max * (k - 1) + k + s.cfg.cap_iq;
+        d->cap_phi = d->gL - 1 + reads;
+        d->cap_sym = (int)(reads / k + 1);
+    }
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_sym = carve((size_t)d->cap_sym * sizeof(uint32_t)), o_bevm = carve((size_t)b->max_blocks * sizeof(float));
-    const size_t o_st = carve((size_t)kDigRecords * 2 * kDigStateFloats * sizeof(float)), o_stash = carve((size_t)2 * kDigFskMaxK * sizeof(float2));
-    const size_t o_map = carve(std::max<size_t>(1, map.size()) * sizeof(uint32_t));
+    const size_t o_sym = carve((size_t)d->cap_sym * sizeof(uint32_t)), o_bevm = carve(gmsk ? 0 : (size_t)b->max_blocks * sizeof(float));
+    const size_t o_st = carve(gmsk ? 0 : (size_t)kDigRecords * 2 * kDigStateFloats * sizeof(float)), o_stash = carve(gmsk ? 0 : (size_t)2 * kDigFskMaxK * sizeof(float2));
+    const size_t o_map = carve(gmsk ? 0 : std::max<size_t>(1, map.size()) * sizeof(uint32_t));
+    const size_t o_gh = carve((size_t)d->gL * sizeof(float)), o_ghist = carve((size_t)2 * (d->gL + 1) * sizeof(float));
+    const size_t o_gblk = carve(gmsk ? ((size_t)b->max_blocks + 1) * sizeof(GmskBlock) : 0), o_gphi = carve((size_t)d->cap_phi * sizeof(float));
+    std::vector<float> taps;
+    if (d->gL) taps = design::gmsk_rx_taps((unsigned)d->gk, (unsigned)d->gm, d->p.bw);
     if (hipMalloc(&d->mem, off) != hipSuccess) { d->mem = nullptr; s.configured = false; return fail(CSDR_ENOMEM, "digital slot of %zu bytes", off); }
     char *base = (char *)d->mem;
     d->sym = (uint32_t *)(base + o_sym); d->bevm = (float *)(base + o_bevm); d->st = (float *)(base + o_st);
     d->stash = (float2 *)(base + o_stash); d->map = (uint32_t *)(base + o_map);
+    d->gh = (float *)(base + o_gh); d->ghist = (float *)(base + o_ghist);
+    d->gblk_d = (GmskBlock *)(base + o_gblk); d->gphi = (float *)(base + o_gphi);
     // modemcf_create: r = x_hat = 0 (EVM 0), DPSK phase 0; fskdem: an empty input buffer.  A failure leaves the slot unconfigured, as above.
-    if (hipMemset(d->mem, 0, off) != hipSuccess || (!map.empty() && hipMemcpy(d->map, map.data(), map.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)) {
+    // gmskdem_create: x_prime = 0 and an empty filter window (zeros)
+    if (hipMemset(d->mem, 0, off) != hipSuccess || (!map.empty() && hipMemcpy(d->map, map.data(), map.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) ||
+        (!taps.empty() && hipMemcpy(d->gh, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)) {
         s.configured = false;
         return fail(CSDR_EHIP, "digital slot initialisation: %s", hipGetErrorString(hipGetLastError()));
     }
@@ -217,12 +261,41 @@ extern "C" int csdr_bank_set_digital_cons(csdr_bank *b, int slot, int cons) {
     return CSDR_OK;
 }
 
+// ModemGMSK::demodulate (ModemGMSK.cpp:116-134) per block of n samples with c = inputBuffer.size() before it: S = c + n, the loop i = 0, k, 2k ..
+// < S / k runs I = ceil((S / k) / k) symbols, symbol j reads the block's samples [j k, j k + k) -- past its end: zero here -- and afterwards
+// c = S - I k.  No blocks planned (a skipped slot): no demodulate call, nothing changes.
+static void gmsk_plan(DigSlot &d, int NB, const BlockPlan *pl) {
+    const int k = d.gk;
+    d.gblk.assign((size_t)NB + 1, GmskBlock{});
+    int32_t off = d.gL - 1, prev = -2, nsym = 0;
+    int64_t c = d.gcarry;
+    for (int bb = 0; bb < NB; ++bb) {
+        csdr_digital_result &r = d.res[bb];
+        r.cons = 2;
+        const int a = pl ? pl[bb].j0 : 0, n = pl ? pl[bb + 1].j0 - a : 0;
+        int64_t I = 0;
+        if (pl) {
+            const int64_t S = c + n, i_max = S / k;
+            I = (i_max + k - 1) / k;
+            c = S - I * k;
+        }
+        r.n_symbols = (int)I; r.symbol_offset = nsym; r.carry = (int32_t)c;
+        d.gblk[bb] = GmskBlock{off, a, n, prev};
+        if (I > 0) { const int64_t last = I * k - 1; prev = last < n ? a + (int32_t)last : -1; }
+        off += (int32_t)(I * k); nsym += (int)I;
+    }
+    d.gblk[NB] = GmskBlock{off, 0, 0, prev};
+    d.nsym_plan = nsym;
+    d.gcarry_new = c;
+}
+
 void bank_digital_plan(csdr_bank *b, int slot, int NB, const BlockPlan *pl) {
     DigSlot &d = *b->slots[slot].dig;
     d.res.assign((size_t)NB, csdr_digital_result{});
     d.n = pl ? pl[NB].j0 : 0;
     d.run_idx = d.idx; d.run_cons = dig_cons_of(d);
     const bool fsk = d.p.kind == CSDR_DIGITAL_FSK;
+    if (d.p.kind == CSDR_DIGITAL_GMSK) { gmsk_plan(d, NB, pl); if (pl) b->dig_run.push_back(slot); else { d.ran = false; d.nsym = 0; } return; }
     for (int bb = 0; bb < NB; ++bb) {
         csdr_digital_result &r = d.res[bb];
         r.cons = d.run_cons;
@@ -240,16 +313,58 @@ void bank_digital_plan(csdr_bank *b, int slot, int NB, const BlockPlan *pl) {
     else { d.ran = false; d.nsym = 0; }
 }
 
+// the GMSK slots of the batch: gmsk_phase, then gmsk_decide, on the audio lane behind the front-end
+static int gmsk_launch(csdr_bank *b, const std::vector<int> &slots) {
+    if (slots.empty()) return CSDR_OK;
+    csdr_ctx *c = b->ctx;
+    const int nj = (int)slots.size();
+    std::vector<GmskJob> &jh = b->gmsk_jobs_h;
+    jh.assign((size_t)nj, GmskJob{});
+    int gx_phase = 1, gx_decide = 1;
+    for (int i = 0; i < nj; ++i) {           // every check first: a refusal leaves every slot as it was
+        const DigSlot &d = *b->slots[slots[i]].dig;
+        const int nb = (int)d.gblk.size() - 1;
+        if (nb > b->max_blocks || d.gblk[nb].off > d.cap_phi || d.nsym_plan > d.cap_sym)
+            return fail(CSDR_ERANGE, "GMSK slot %d: %d phase differences / %d symbols exceed its buffers", slots[i], d.gblk[nb].off, d.nsym_plan);
+    }
+    if (int rc = b->gmsk_jobs.reserve((size_t)b->max_demods)) return rc;
+    for (int i = 0; i < nj; ++i) {
+        SlotHost &s = b->slots[slots[i]];
+        DigSlot &d = *s.dig;
+        const int nb = (int)d.gblk.size() - 1;
+        const int n_stream = d.gblk[nb].off;
+        GmskJob &j = jh[i];
+        j.iq = s.cfg.iq + (size_t)s.last_parity * ((size_t)kIqHist + s.cfg.cap_iq) + kIqHist;     // the batch's resampled IQ (csdr_bank_fetch_iq)
+        j.blk = d.gblk_d; j.nb = nb; j.L = d.gL; j.k = d.gk; j.nsym = d.nsym_plan; j.h = d.gh;
+        j.hist_rd = d.ghist + (size_t)d.hist_cur * (d.gL + 1); j.hist_wr = d.ghist + (size_t)(d.hist_cur ^ 1) * (d.gL + 1);
+        j.phi = d.gphi; j.sym = d.sym; j.soft = nullptr;
+        gx_phase = std::max(gx_phase, (n_stream + kGmskThreads - 1) / kGmskThreads);
+        gx_decide = std::max(gx_decide, (d.nsym_plan + kGmskThreads / 64 - 1) / (kGmskThreads / 64));
+        CSDR_HIP_TRY(hipMemcpyAsync(d.gblk_d, d.gblk.data(), d.gblk.size() * sizeof(GmskBlock), hipMemcpyHostToDevice, c->lanes[LANE_AUDIO]));
+        d.hist_cur ^= 1; d.gcarry = d.gcarry_new; d.nsym = d.nsym_plan; d.ran = true;
+    }
+    CSDR_HIP_TRY(hipMemcpyAsync(b->gmsk_jobs.p, jh.data(), (size_t)nj * sizeof(GmskJob), hipMemcpyHostToDevice, c->lanes[LANE_AUDIO]));
+    CSDR_LAUNCH(c, LANE_AUDIO, KID_DIGITAL, gmsk_phase, dim3(gx_phase, nj), dim3(kGmskThreads), 0, (const GmskJob *)b->gmsk_jobs.p);
+    CSDR_HIP_TRY(hipGetLastError());
+    CSDR_LAUNCH(c, LANE_AUDIO, KID_DIGITAL, gmsk_decide, dim3(gx_decide, nj), dim3(kGmskThreads), 0, (const GmskJob *)b->gmsk_jobs.p);
+    CSDR_HIP_TRY(hipGetLastError());
+    return CSDR_OK;
+}
+
 int bank_digital_launch(csdr_bank *b, const BlockPlan *plans_d, int NB) {
     if (b->dig_run.empty()) return CSDR_OK;
     csdr_ctx *c = b->ctx;
-    const int nj = (int)b->dig_run.size();
+    std::vector<int> run, gmsk;
+    for (int si : b->dig_run) (b->slots[si].dig->p.kind == CSDR_DIGITAL_GMSK ? gmsk : run).push_back(si);
+    if (int rc = gmsk_launch(b, gmsk)) return rc;
+    if (run.empty()) return CSDR_OK;
+    const int nj = (int)run.size();
     if (int rc = b->dig_jobs.reserve((size_t)b->max_demods * sizeof(DigJob))) return rc;
     b->dig_jobs_h.assign((size_t)nj * sizeof(DigJob), 0);
     DigJob *jh = reinterpret_cast<DigJob *>(b->dig_jobs_h.data());
     int gx = 1;
     for (int i = 0; i < nj; ++i) {
-        const int si = b->dig_run[i];
+        const int si = run[i];
         SlotHost &s = b->slots[si];
         DigSlot &d = *s.dig;
         DigJob &j = jh[i];
@@ -378,5 +493,59 @@ extern "C" int csdr_digital_run(csdr_ctx *c, const csdr_digital_params *dp, int6
     }
     *n_symbols = nsym;
     if (evm_last) *evm_last = evm;
+    return CSDR_OK;
+}
+
+extern "C" int csdr_gmsk_run(csdr_ctx *c, const csdr_digital_params *dp, const float *iq_host, int n, csdr_gmsk_state *state, float *history,
+                             uint32_t *sym_host, float *soft_host, int cap_symbols, int *n_symbols) {
+    DeviceScope dev__(c);
+    if (!c || !dp || !state || !history || !n_symbols || n < 0 || (n > 0 && !iq_host)) return fail(CSDR_EINVAL, "bad argument");
+    if (dp->kind != CSDR_DIGITAL_GMSK) return fail(CSDR_EINVAL, "csdr_gmsk_run: kind must be CSDR_DIGITAL_GMSK");
+    DigSlot d;
+    std::vector<uint32_t> map;
+    if (int rc = dig_setup(dp, 500, &d, &map)) return rc;
+    const int k = d.gk, L = d.gL;
+    if (n % k) return fail(CSDR_EINVAL, "csdr_gmsk_run: %d samples are not whole symbols of %d", n, k);
+    const int nsym = n / k;
+    if (nsym > cap_symbols || (nsym > 0 && !sym_host)) return fail(CSDR_ERANGE, "need room for %d symbols", nsym);
+    const std::vector<float> taps = design::gmsk_rx_taps((unsigned)k, (unsigned)d.gm, d.p.bw);
+    const GmskBlock blk[2] = {{L - 1, 0, n, -2}, {L - 1 + n, 0, 0, n > 0 ? n - 1 : -2}};
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_job = carve(sizeof(GmskJob)), o_blk = carve(sizeof blk), o_h = carve((size_t)L * sizeof(float)),
+                 o_hist = carve((size_t)2 * (L + 1) * sizeof(float)), o_iq = carve((size_t)std::max(1, n) * sizeof(float2)),
+                 o_phi = carve((size_t)(L - 1 + n) * sizeof(float)), o_sym = carve((size_t)std::max(1, nsym) * sizeof(uint32_t)),
+                 o_soft = carve((size_t)std::max(1, nsym) * sizeof(float));
+    void *mem = nullptr;
+    if (hipMalloc(&mem, off) != hipSuccess) return fail(CSDR_ENOMEM, "%zu bytes", off);
+    std::unique_ptr<void, void (*)(void *)> guard(mem, [](void *p) { (void)hipFree(p); });
+    char *base = (char *)mem;
+    hipStream_t st = c->lanes[LANE_AUDIO];
+    std::vector<float> hist((size_t)L + 1);
+    memcpy(hist.data(), history, (size_t)(L - 1) * sizeof(float));
+    hist[L - 1] = state->x_prime[0]; hist[L] = state->x_prime[1];
+    GmskJob j{};
+    j.iq = (const float2 *)(base + o_iq); j.blk = (const GmskBlock *)(base + o_blk); j.nb = 1; j.L = L; j.k = k; j.nsym = nsym;
+    j.h = (const float *)(base + o_h); j.hist_rd = (const float *)(base + o_hist); j.hist_wr = (float *)(base + o_hist) + (L + 1);
+    j.phi = (float *)(base + o_phi); j.sym = (uint32_t *)(base + o_sym); j.soft = (float *)(base + o_soft);
+    CSDR_HIP_TRY(hipMemcpyAsync(base + o_job, &j, sizeof j, hipMemcpyHostToDevice, st));
+    CSDR_HIP_TRY(hipMemcpyAsync(base + o_blk, blk, sizeof blk, hipMemcpyHostToDevice, st));
+    CSDR_HIP_TRY(hipMemcpyAsync(base + o_h, taps.data(), (size_t)L * sizeof(float), hipMemcpyHostToDevice, st));
+    CSDR_HIP_TRY(hipMemcpyAsync(base + o_hist, hist.data(), hist.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    if (n) CSDR_HIP_TRY(hipMemcpyAsync(base + o_iq, iq_host, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, st));
+    const int gx_phase = (L - 1 + n + kGmskThreads - 1) / kGmskThreads, gx_decide = std::max(1, (nsym + kGmskThreads / 64 - 1) / (kGmskThreads / 64));
+    CSDR_LAUNCH(c, LANE_AUDIO, KID_DIGITAL, gmsk_phase, dim3(gx_phase, 1), dim3(kGmskThreads), 0, (const GmskJob *)(base + o_job));
+    CSDR_HIP_TRY(hipGetLastError());
+    CSDR_LAUNCH(c, LANE_AUDIO, KID_DIGITAL, gmsk_decide, dim3(gx_decide, 1), dim3(kGmskThreads), 0, (const GmskJob *)(base + o_job));
+    CSDR_HIP_TRY(hipGetLastError());
+    if (nsym) {
+        CSDR_HIP_TRY(hipMemcpyAsync(sym_host, base + o_sym, (size_t)nsym * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (soft_host) CSDR_HIP_TRY(hipMemcpyAsync(soft_host, base + o_soft, (size_t)nsym * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    CSDR_HIP_TRY(hipMemcpyAsync(hist.data(), base + o_hist + (size_t)(L + 1) * sizeof(float), hist.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    CSDR_HIP_TRY(hipStreamSynchronize(st));
+    memcpy(history, hist.data(), (size_t)(L - 1) * sizeof(float));
+    state->x_prime[0] = hist[L - 1]; state->x_prime[1] = hist[L];
+    *n_symbols = nsym;
     return CSDR_OK;
 }

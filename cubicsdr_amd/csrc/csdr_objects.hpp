@@ -10,6 +10,7 @@
 #include "kernels_post.hpp"
 #include "kernels_chanfft.hpp"
 #include "kernels_demod.hpp"
+#include "kernels_digital.hpp"
 
 using namespace csdr;      // (this header is only included by the library's own translation units, all of which do the same)
 
@@ -127,6 +128,8 @@ struct csdr_bank {
     std::vector<int> dig_run;                // digital slots of the batch being planned (csdr_digital.hip)
     DevBuf<char> dig_jobs;                   // their launch records
     std::vector<char> dig_jobs_h;
+    DevBuf<GmskJob> gmsk_jobs;               // the GMSK slots' launch records
+    std::vector<GmskJob> gmsk_jobs_h;
 };
 
 // internal modem id: NCO + msresamp only, no modem / audio stage (the zoomed spectrum view's shift + resample, SpectrumVisualProcessor.cpp:306-379)

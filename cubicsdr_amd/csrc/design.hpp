@@ -7,6 +7,7 @@
 // integer such as a filter length or a phase step) and uploads them once per
 // (re)configuration.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -420,6 +421,149 @@ inline std::vector<float> hilbert_taps(unsigned m, float as) {
         hq.push_back(h[i] * std::sin(0.5f * kPi * t));
     }
     return hq;
+}
+
+// ---- GMSK (ModemGMSK.cpp: gmskdem_create(k, m, BT)): the transmit pulse and the receive filter, h_len = 2 k m + 1 taps each ---------------
+// liquid_firdes_gmsktx: the Gaussian-filtered rectangle of one symbol, Q(2 pi BT (t - 1/2) / sqrt(ln 2)) - Q(2 pi BT (t + 1/2) / sqrt(ln 2)) at
+// t = i / k - m, scaled to integrate to pi / 2 per symbol, times k.  liquid_firdes_gmskrx: the ratio of the spectra of a Kaiser Nyquist prototype
+// (cut-off 1 / 2k, transition BT / k, stop-band from its length) and of that pulse, each lifted by its minimum plus 1e-3, times a Kaiser
+// low-pass (cut-off (0.7 + 0.1 BT) / k, 60 dB) normalised to its DC value, back in time and scaled by k^2 / (k h_len).  That ratio is
+// ill-conditioned where both spectra lie near their minima -- float32 steps move the taps by up to a few 1e-3 of the peak (14 % in liquid's own
+// float design at k 512, m 8, BT 0.1) -- so everything here is evaluated in double, the h_len-point (odd) DFTs by Bluestein's method over a
+// power-of-two FFT, and only the taps are rounded to float.
+inline double q_function(double z) { return 0.5 * std::erfc(z * 0.70710678118654752440); }
+
+inline double bessel_i0(double z) {          // sum ((z / 2)^k / k!)^2 to double precision
+    const double q = 0.25 * z * z;
+    double t = 1.0, acc = 1.0;
+    for (int k = 1; k < 500 && t > 1e-17 * acc; ++k) { t *= q / ((double)k * k); acc += t; }
+    return acc;
+}
+
+// the stop-band attenuation whose Kaiser length estimate reaches n taps at transition width df (bisection over (0.01, 200) dB, 20 steps)
+inline double required_filter_as(double df, unsigned n) {
+    double as0 = 0.01, as1 = 200.0, as = 0.0;
+    for (int i = 0; i < 20; ++i) {
+        as = 0.5 * (as1 + as0);
+        if ((double)(unsigned)((as - 7.95) / (14.26 * df)) < (double)n) as0 = as;
+        else as1 = as;
+    }
+    return as;
+}
+
+// the Kaiser-windowed sinc low-pass of liquid_firdes_kaiser in double
+inline std::vector<double> kaiser_lowpass_d(unsigned n, double fc, double as) {
+    as = std::fabs(as);
+    const double beta = as > 50.0 ? 0.1102 * (as - 8.7) : as > 21.0 ? 0.5842 * std::pow(as - 21.0, 0.4) + 0.07886 * (as - 21.0) : 0.0;
+    const double i0b = bessel_i0(beta);
+    std::vector<double> h(n);
+    for (unsigned i = 0; i < n; ++i) {
+        const double t = (double)i - (double)(n - 1) / 2.0, r = 2.0 * t / (double)(n - 1), x = 2.0 * fc * t;
+        const double sinc = x == 0.0 ? 1.0 : std::sin(M_PI * x) / (M_PI * x);
+        h[i] = sinc * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
+    }
+    return h;
+}
+
+// in-place radix-2 forward transform of a power-of-two length; tw: exp(-2 pi i j / n), j < n / 2
+inline void fft_pow2(std::vector<std::complex<double>> &a, const std::vector<std::complex<double>> &tw) {
+    const size_t n = a.size();
+    for (size_t i = 1, j = 0; i < n; ++i) {
+        size_t bit = n >> 1;
+        for (; j & bit; bit >>= 1) j ^= bit;
+        j ^= bit;
+        if (i < j) std::swap(a[i], a[j]);
+    }
+    for (size_t len = 2; len <= n; len <<= 1) {
+        const size_t h = len / 2, step = n / len;
+        for (size_t i = 0; i < n; i += len)
+            for (size_t k = 0; k < h; ++k) {
+                const std::complex<double> u = a[i + k], v = a[i + k + h] * tw[k * step];
+                a[i + k] = u + v; a[i + k + h] = u - v;
+            }
+    }
+}
+
+// n-point DFTs of any length in double: Bluestein's chirp convolution over a power-of-two transform (the chirp's transform made once)
+struct DftAny {
+    size_t n, L;
+    std::vector<std::complex<double>> chirp, B, tw;
+    explicit DftAny(size_t n_) : n(n_), L(1) {
+        while (L < 2 * n - 1) L <<= 1;
+        tw.resize(L / 2);
+        for (size_t j = 0; j < L / 2; ++j) tw[j] = std::polar(1.0, -2.0 * M_PI * (double)j / (double)L);
+        chirp.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            const uint64_t i2 = ((uint64_t)i * i) % (2 * (uint64_t)n);     // exp(-i pi i^2 / n), the square reduced exactly
+            chirp[i] = std::polar(1.0, -M_PI * (double)i2 / (double)n);
+        }
+        B.assign(L, 0.0);
+        B[0] = std::conj(chirp[0]);
+        for (size_t i = 1; i < n; ++i) B[i] = B[L - i] = std::conj(chirp[i]);
+        fft_pow2(B, tw);
+    }
+    // sign -1: forward, +1: backward (unnormalised)
+    std::vector<std::complex<double>> run(const std::vector<std::complex<double>> &x, int sign) const {
+        std::vector<std::complex<double>> a(L);
+        for (size_t i = 0; i < n; ++i) a[i] = (sign < 0 ? x[i] : std::conj(x[i])) * chirp[i];
+        fft_pow2(a, tw);
+        for (size_t i = 0; i < L; ++i) a[i] = std::conj(a[i] * B[i]);         // the inverse transform as the conjugate of a forward one
+        fft_pow2(a, tw);
+        std::vector<std::complex<double>> y(n);
+        for (size_t i = 0; i < n; ++i) {
+            const std::complex<double> v = std::conj(a[i]) / (double)L * chirp[i];
+            y[i] = sign < 0 ? v : std::conj(v);
+        }
+        return y;
+    }
+};
+
+inline std::vector<double> gmsk_tx_taps_d(unsigned k, unsigned m, double bt) {
+    const unsigned n = 2 * k * m + 1;
+    std::vector<double> h(n);
+    const double c0 = 1.0 / std::sqrt(std::log(2.0));
+    double e = 0.0;
+    for (unsigned i = 0; i < n; ++i) {
+        const double t = (double)i / (double)k - (double)m;
+        h[i] = q_function(2 * M_PI * bt * (t - 0.5) * c0) - q_function(2 * M_PI * bt * (t + 0.5) * c0);
+        e += h[i];
+    }
+    for (unsigned i = 0; i < n; ++i) h[i] *= M_PI / (2.0 * e) * (double)k;
+    return h;
+}
+
+inline std::vector<float> gmsk_tx_taps(unsigned k, unsigned m, float bt) {
+    const std::vector<double> h = gmsk_tx_taps_d(k, m, bt);
+    return std::vector<float>(h.begin(), h.end());
+}
+
+inline std::vector<float> gmsk_rx_taps(unsigned k, unsigned m, float bt_f) {
+    const unsigned n = 2 * k * m + 1, km = k * m;
+    const double bt = bt_f;
+    const std::vector<double> ht = gmsk_tx_taps_d(k, m, bt);
+    const std::vector<double> hp = kaiser_lowpass_d(n, 0.5 / k, required_filter_as(bt / k, n));    // the Nyquist prototype
+    const std::vector<double> gp = kaiser_lowpass_d(n, (0.7 + 0.1 * bt) / k, 60.0);                 // the stop-band gain
+    std::vector<std::complex<double>> a(n), b(n), c(n);
+    for (unsigned i = 0; i < n; ++i) {              // centred on index 0: zero phase, real spectra
+        const unsigned j = (i + km) % n;
+        a[i] = hp[j]; b[i] = gp[j]; c[i] = ht[j];
+    }
+    const DftAny dft(n);
+    const auto Hp = dft.run(a, -1), Gp = dft.run(b, -1), Ht = dft.run(c, -1);
+    double hp_min = 0, gp_min = 0, ht_min = 0;
+    for (unsigned i = 0; i < n; ++i) {
+        if (i == 0 || Ht[i].real() < ht_min) ht_min = Ht[i].real();
+        if (i == 0 || Hp[i].real() < hp_min) hp_min = Hp[i].real();
+        if (i == 0 || Gp[i].real() < gp_min) gp_min = Gp[i].real();
+    }
+    const double delta = 1e-3;
+    std::vector<std::complex<double>> H(n);
+    for (unsigned i = 0; i < n; ++i)
+        H[i] = (Hp[i].real() - hp_min + delta) / (Ht[i].real() - ht_min + delta) * ((Gp[i].real() - gp_min) / Gp[0].real());
+    const auto hh = dft.run(H, +1);
+    std::vector<float> h(n);
+    for (unsigned i = 0; i < n; ++i) h[i] = (float)(hh[(i + km + 1) % n].real() / (double)(k * n) * (double)k * (double)k);
+    return h;
 }
 
 // ---- block / channel sizing rules of the reference's SDR thread (SoapySDRThread.cpp:668-693) ---------------

@@ -46,5 +46,16 @@ int csdr_design_fms_output_fir(int audio_rate, int demph_us, float *g, unsigned 
 void csdr_design_hilbert(unsigned m, float as, float *hq) { auto v = hilbert_taps(m, as); std::memcpy(hq, v.data(), v.size() * sizeof(float)); }
 int csdr_design_channel_count(long long rate) { return optimal_channel_count(rate); }
 int csdr_design_element_count(long long rate, int fps, int nch) { return optimal_element_count(rate, fps, nch); }
+// gmskdem_create(k, m, bt)'s filters: h_len = 2 k m + 1 taps each into tx / rx (cap floats each); returns h_len, -1 where gmskdem_create
+// refuses or beyond the settings' ranges (k > 512, m > 128), -2 when cap is too small
+int csdr_design_gmsk(int k, int m, float bt, float *tx, float *rx, int cap) {
+    if (k < 2 || m < 1 || !(bt > 0.0f && bt < 1.0f) || k > 512 || m > 128) return -1;
+    const int n = 2 * k * m + 1;
+    if (n > cap) return -2;
+    const auto t = gmsk_tx_taps((unsigned)k, (unsigned)m, bt), r = gmsk_rx_taps((unsigned)k, (unsigned)m, bt);
+    std::memcpy(tx, t.data(), (size_t)n * sizeof(float));
+    std::memcpy(rx, r.data(), (size_t)n * sizeof(float));
+    return n;
+}
 
 }  // extern "C"

@@ -14,7 +14,7 @@
 
 namespace csdr {
 
-enum DigScheme : int32_t { DIG_PSK = 0, DIG_DPSK, DIG_ASK, DIG_QAM, DIG_BPSK, DIG_QPSK, DIG_OOK, DIG_FSK };
+enum DigScheme : int32_t { DIG_PSK = 0, DIG_DPSK, DIG_ASK, DIG_QAM, DIG_BPSK, DIG_QPSK, DIG_OOK, DIG_FSK, DIG_GMSK };
 
 constexpr int kDigThreads = 256;
 constexpr int kDigFskMaxK = 2048;          // fskdem samples per symbol (its create rule: k <= 2^11)
@@ -207,6 +207,95 @@ CSDR_KERNEL __launch_bounds__(kDigThreads) void digital_demod(const DigJob *__re
             }
             j.bevm[bb] = e;
         }
+    }
+}
+
+// ---- GMSK (ModemGMSK.cpp:116-134, gmskdem(k, m, BT)): per symbol of k samples, the phase differences arg(conj(x_prev) x) go through the
+// receive filter (h_len = 2 k m + 1 taps, no equaliser) and the filter output after the symbol's FIRST push is decided by its sign (> 0: 1).
+// Two launches cover every GMSK slot and block of a batch.  gmsk_phase writes each slot's phase-difference stream: the h_len - 1
+// values carried from the previous batch, then every block's processed range in order.  A block's range is the I k samples its I symbols read
+// from the block's start; samples at or past the block's end read as zero, and the first sample's x_prev is the last sample the previous symbol
+// read.  gmsk_decide then takes one wave per symbol over that stream and keeps the last h_len - 1 values for the next batch.
+constexpr int kGmskThreads = 256;
+
+struct GmskBlock {
+    int32_t off;     // stream position of the block's first processed sample ([nb]: the stream's length)
+    int32_t j0, n;   // the block's samples in the batch IQ
+    int32_t prev;    // x_prev of its first processed sample: a batch IQ index, -1 (zero: a sample past an earlier block's end) or -2 (the carried
+                     // x_prime); [nb]: the x_prime after the batch
+};
+
+struct GmskJob {
+    const float2 *iq;          // this batch's resampled IQ
+    const GmskBlock *blk;      // [nb + 1]
+    int32_t nb, L, k, nsym;    // blocks, taps, samples per symbol, symbols of the batch
+    const float *h;            // [L] receive filter
+    const float *hist_rd;      // [L - 1] phase differences carried in (oldest first), then x_prime (2)
+    float *hist_wr;            // the same after the batch (the other copy)
+    float *phi;                // [blk[nb].off] the phase-difference stream
+    uint32_t *sym;             // [nsym] decisions
+    float *soft;               // [nsym] filter outputs, or null
+};
+
+// arg(conj(a) b) as the reference's object evaluates it: re = a.x b.x + a.y b.y, im = a.x b.y - a.y b.x -- with an exact zero operand the signs
+// of the zero products decide between 0 and pi
+__host__ __device__ __forceinline__ float gmsk_phase_diff(float2 a, float2 b) {
+    const float re = a.x * b.x + a.y * b.y, im = a.x * b.y - a.y * b.x;
+    return atan2f(im, re);
+}
+
+__device__ __forceinline__ float2 gmsk_sample(const GmskJob &j, const GmskBlock &bk, int u) {
+    return u < bk.n ? j.iq[bk.j0 + u] : make_float2(0.0f, 0.0f);
+}
+
+__device__ __forceinline__ float2 gmsk_prev_of(const GmskJob &j, int32_t prev) {
+    if (prev >= 0) return j.iq[prev];
+    if (prev == -2) return make_float2(j.hist_rd[j.L - 1], j.hist_rd[j.L]);
+    return make_float2(0.0f, 0.0f);
+}
+
+// grid (workgroups, jobs), kGmskThreads threads: one thread per stream position
+CSDR_KERNEL __launch_bounds__(kGmskThreads) void gmsk_phase(const GmskJob *__restrict__ jobs) {
+    const GmskJob &j = jobs[blockIdx.y];
+    const int t = blockIdx.x * kGmskThreads + threadIdx.x;
+    if (t == 0) {
+        const float2 xp = gmsk_prev_of(j, j.blk[j.nb].prev);
+        j.hist_wr[j.L - 1] = xp.x; j.hist_wr[j.L] = xp.y;
+    }
+    const int n_stream = j.blk[j.nb].off;
+    if (t >= n_stream) return;
+    if (t < j.L - 1) { j.phi[t] = j.hist_rd[t]; return; }
+    int lo = 0, hi = j.nb - 1;                       // the last block starting at or before t (empty blocks share the next one's start)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (j.blk[mid].off <= t) lo = mid;
+        else hi = mid - 1;
+    }
+    const GmskBlock bk = j.blk[lo];
+    const int u = t - bk.off;
+    const float2 x = gmsk_sample(j, bk, u), xp = u == 0 ? gmsk_prev_of(j, bk.prev) : gmsk_sample(j, bk, u - 1);
+    j.phi[t] = gmsk_phase_diff(xp, x);
+}
+
+// grid (workgroups, jobs), kGmskThreads threads: wave w of workgroup x decides symbol 4 x + w, lanes striding the taps; workgroup 0 also keeps
+// the stream's last L - 1 values
+CSDR_KERNEL __launch_bounds__(kGmskThreads) void gmsk_decide(const GmskJob *__restrict__ jobs) {
+    const GmskJob &j = jobs[blockIdx.y];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int s = blockIdx.x * (kGmskThreads / 64) + (tid >> 6);
+    if (s < j.nsym) {
+        const float *x = j.phi + (j.L - 1) + (int64_t)s * j.k;       // the symbol's first push: h[i] meets the value i pushes before it
+        float acc = 0.0f;
+        for (int i = lane; i < j.L; i += 64) acc += j.h[i] * x[-i];
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        if (lane == 0) {
+            j.sym[s] = acc > 0.0f ? 1u : 0u;
+            if (j.soft) j.soft[s] = acc;
+        }
+    }
+    if (blockIdx.x == 0) {
+        const float *src = j.phi + (j.blk[j.nb].off - (j.L - 1));
+        for (int i = tid; i < j.L - 1; i += kGmskThreads) j.hist_wr[i] = src[i];
     }
 }
 

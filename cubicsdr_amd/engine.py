@@ -211,9 +211,9 @@ class SDRPost:
             self.h = C.c_void_p()
 
 
-def digital_params(kind, cons=0, bps=0, sps=0, bw=0.0):
+def digital_params(kind, cons=0, bps=0, sps=0, bw=0.0, fdelay=0):
     k = H.DIGITAL_BY_NAME[kind] if isinstance(kind, str) else int(kind)
-    return H.DigitalParams(k, int(cons), int(bps), int(sps), float(bw))
+    return H.DigitalParams(k, int(cons), int(bps), int(sps), float(bw), int(fdelay))
 
 
 def digital_run(ctx, kind, iq, sample_rate, state=None, cons=0, bps=0, sps=0, bw=0.0):
@@ -227,6 +227,24 @@ def digital_run(ctx, kind, iq, sample_rate, state=None, cons=0, bps=0, sps=0, bw
     H.check(H.lib().csdr_digital_run(ctx.h, C.byref(d), int(sample_rate), x.ctypes.data_as(C.c_void_p), int(x.size), C.byref(st),
                                      out.ctypes.data_as(C.c_void_p), int(out.size), C.byref(n), C.byref(evm)))
     return out[:n.value].copy(), evm.value, st
+
+
+def gmsk_run(ctx, iq, state=None, sps=0, fdelay=0, ebf=0.0):
+    """csdr_gmsk_run: the GMSK kernels alone on `iq` (complex64, whole symbols of `sps` samples), len(iq) / sps consecutive gmskdem_demodulate
+    calls of one object; 0 = the reference default (sps 4, fdelay 3, ebf 0.3).  `state`: (H.GmskState, history float32[2 sps fdelay]) from an
+    earlier call, None = a fresh object.  Returns (symbols uint32, soft float32: the filter output each was decided from, state)."""
+    d = digital_params("GMSK", sps=sps, bw=ebf, fdelay=fdelay)
+    k, m = d.sps or 4, d.fdelay or 3
+    x = np.ascontiguousarray(iq, dtype=np.complex64)
+    st, hist = state if state is not None else (H.GmskState(), np.zeros(max(1, 2 * k * m), np.float32))
+    if not isinstance(hist, np.ndarray) or hist.dtype != np.float32 or not hist.flags.c_contiguous or hist.size != max(1, 2 * k * m):
+        raise ValueError("gmsk_run: the state's history must be float32[2 sps fdelay] = %d for these settings" % (2 * k * m))
+    n_sym = x.size // k
+    sym, soft = np.empty(max(1, n_sym), np.uint32), np.empty(max(1, n_sym), np.float32)
+    n = C.c_int()
+    H.check(H.lib().csdr_gmsk_run(ctx.h, C.byref(d), x.ctypes.data_as(C.c_void_p), int(x.size), C.byref(st), hist.ctypes.data_as(C.c_void_p),
+                                  sym.ctypes.data_as(C.c_void_p), soft.ctypes.data_as(C.c_void_p), int(sym.size), C.byref(n)))
+    return sym[:n.value].copy(), soft[:n.value].copy(), (st, hist)
 
 
 class DemodBank:
@@ -245,11 +263,12 @@ class DemodBank:
         p = H.DemodParams(m, int(bandwidth), int(audio_sample_rate), int(modem_arg), int(frequency))
         H.check(self._l.csdr_bank_configure_slot(self.h, int(slot), C.byref(p), post.h))
 
-    def configure_digital(self, slot, post, kind, bandwidth, frequency, cons=0, bps=0, sps=0, bw=0.0, audio_sample_rate=48000):
-        """a digital-lab modem (kind: "PSK", "DPSK", "ASK", "QAM", "BPSK", "QPSK", "OOK", "FSK" or CSDR_DIGITAL_*); 0 = the reference default"""
+    def configure_digital(self, slot, post, kind, bandwidth, frequency, cons=0, bps=0, sps=0, bw=0.0, audio_sample_rate=48000, fdelay=0, ebf=None):
+        """a digital-lab modem (kind: "PSK", "DPSK", "ASK", "QAM", "BPSK", "QPSK", "OOK", "FSK", "GMSK" or CSDR_DIGITAL_*); 0 = the reference
+        default.  GMSK: sps = samples per symbol, fdelay, ebf (= bw)"""
         k = H.DIGITAL_BY_NAME[kind] if isinstance(kind, str) else int(kind)
         p = H.DemodParams(H.CSDR_MODEM_DIGITAL, int(bandwidth), int(audio_sample_rate), 0, int(frequency))
-        d = digital_params(k, cons, bps, sps, bw)
+        d = digital_params(k, cons, bps, sps, bw if ebf is None else ebf, fdelay)
         H.check(self._l.csdr_bank_configure_digital_slot(self.h, int(slot), C.byref(p), C.byref(d), post.h))
 
     def set_digital_cons(self, slot, cons):

@@ -17,7 +17,8 @@ CSDR_SPEC_FIRST_FRAME, CSDR_SPEC_CONTIGUOUS, CSDR_SPEC_LINES = 0, 1, 2
 MODEM_BY_NAME = {"NBFM": 0, "FM": 1, "AM": 2, "USB": 3, "LSB": 4, "I/Q": 5, "IQ": 5, "CW": 6, "DSB": 7, "FMS": 8, "HOST": 9}
 CSDR_MODEM_DIGITAL = 10
 CSDR_DIGITAL_PSK, CSDR_DIGITAL_DPSK, CSDR_DIGITAL_ASK, CSDR_DIGITAL_QAM, CSDR_DIGITAL_BPSK, CSDR_DIGITAL_QPSK, CSDR_DIGITAL_OOK, CSDR_DIGITAL_FSK = range(8)
-DIGITAL_BY_NAME = {"PSK": 0, "DPSK": 1, "ASK": 2, "QAM": 3, "BPSK": 4, "QPSK": 5, "OOK": 6, "FSK": 7}
+CSDR_DIGITAL_GMSK = 8
+DIGITAL_BY_NAME = {"PSK": 0, "DPSK": 1, "ASK": 2, "QAM": 3, "BPSK": 4, "QPSK": 5, "OOK": 6, "FSK": 7, "GMSK": 8}
 CSDR_DIGITAL_MAX_CARRY = 2048
 
 
@@ -35,12 +36,16 @@ class BlockResult(C.Structure):
 
 class DigitalParams(C.Structure):
     _fields_ = [("kind", C.c_int32), ("cons", C.c_int32), ("bps", C.c_int32), ("sps", C.c_int32), ("bw", C.c_float),
-                ("reserved", C.c_int32 * 3)]
+                ("fdelay", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class DigitalResult(C.Structure):
     _fields_ = [("n_symbols", C.c_int32), ("symbol_offset", C.c_int32), ("lock", C.c_int32), ("evm", C.c_float),
                 ("carry", C.c_int32), ("cons", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class GmskState(C.Structure):
+    _fields_ = [("x_prime", C.c_float * 2), ("reserved", C.c_int32 * 2)]
 
 
 class DigitalState(C.Structure):
@@ -192,6 +197,7 @@ ABI = {
     "csdr_bank_fetch_digital_results": (_i, [_p, _i, C.POINTER(DigitalResult), _i, C.POINTER(_i)]),
     "csdr_bank_fetch_symbols": (_i, [_p, _i, _p, _i, C.POINTER(_i)]),
     "csdr_digital_run": (_i, [_p, C.POINTER(DigitalParams), _i64, _p, _i, C.POINTER(DigitalState), _p, _i, C.POINTER(_i), C.POINTER(_f)]),
+    "csdr_gmsk_run": (_i, [_p, C.POINTER(DigitalParams), _p, _i, C.POINTER(GmskState), _p, _p, _p, _i, C.POINTER(_i)]),
 }
 
 _lib = None

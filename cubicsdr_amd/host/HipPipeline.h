@@ -485,7 +485,8 @@ private:
             if (!md) return;
             bandwidth = d.bandwidth_;
             kitRate = d.kit_ ? d.kit_->sampleRate : bandwidth;
-            fsk = md->csdrDigitalParams().kind == CSDR_DIGITAL_FSK;
+            const int kind = md->csdrDigitalParams().kind;
+            fsk = kind == CSDR_DIGITAL_FSK || kind == CSDR_DIGITAL_GMSK;          // text, no lock (GMSK's symbols print as 0 / 1)
             vis = d.audioVisQueue_;
             if (!fsk) md->setDemodulatorLock(dr.lock != 0);
         }

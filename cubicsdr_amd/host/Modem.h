@@ -35,8 +35,18 @@ public:
     long long sampleRate = 0;
     virtual ~ModemIQData() = default;
 };
-struct ModemArgInfo {                                                         // ModemArgInfo of Modem.h:22-60, the fields FM stereo's setting uses
+struct ModemRange {                                                           // ModemRange of Modem.h:12-20
+    ModemRange(double minimum = 0, double maximum = 0) : _min(minimum), _max(maximum) {}
+    double minimum() const { return _min; }
+    double maximum() const { return _max; }
+    double _min, _max;
+};
+
+struct ModemArgInfo {                                                         // ModemArgInfo of Modem.h:22-60, the fields FM stereo's and GMSK's settings use
+    enum class Type { BOOL, INT, FLOAT, STRING, PATH_DIR, PATH_FILE, COLOR };
     std::string key, value, name, description, units;
+    Type type = Type::STRING;
+    ModemRange range;
     std::vector<std::string> options, optionNames;
 };   // the analog modems publish no settings but FM-stereo's de-emphasis
 typedef std::vector<ModemArgInfo> ModemArgInfoList;
@@ -106,6 +116,7 @@ public:
 
     static void registerBuiltins();
     static void registerDigitalLab();        // ModemDigital.h: the digital lab's modems (the reference's ENABLE_DIGITAL_LAB), opt-in
+    static void registerDigitalGMSK();       // ModemDigital.h: the lab's GMSK, opt-in on its own
 
 private:
     static ModemFactoryList &factories() { static ModemFactoryList f; return f; }

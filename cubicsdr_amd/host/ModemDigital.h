@@ -3,8 +3,8 @@
 // csdr_digital_params of the bank slot; the decisions run on the device (csdr_bank_execute).  What the reference keeps in the modem
 // object and the application reads back -- the lock (ModemDigital.cpp:43-53) and the console output (ModemDigitalOutput) -- stays here:
 // SDRPostThread::finishDemod sets the lock from the block's csdr_digital_result and hands FSK's text to the output.
-// Registration is opt-in like the reference's build switch: Modem::registerDigitalLab().  APSK, SQAM, ST (V.29) and GMSK are not built
-// (DESIGN 9); they remain available as host plug-ins through Modem::addModemFactory.
+// Registration is opt-in like the reference's build switch: Modem::registerDigitalLab(), and Modem::registerDigitalGMSK() for GMSK.  APSK, SQAM
+// and ST (V.29) are not built; they remain available as host plug-ins through Modem::addModemFactory.
 #pragma once
 #include <atomic>
 #include <cmath>
@@ -173,6 +173,58 @@ private:
     std::atomic<int> bps_{1}, sps_{9600};                                                 // ModemFSK.cpp:7-12
     std::atomic<float> bw_{0.45f};
 };
+
+// ModemGMSK (ModemGMSK.cpp): fdelay / sps (samples per symbol) / ebf, each write asks for a rebuild (a fresh gmskdem and an empty inputBuffer);
+// the symbols go to the output as hex digits (0 / 1), the lock is never updated
+class ModemGMSK : public ModemDigital {
+public:
+    static ModemBase *factory() { return new ModemGMSK(); }
+    std::string getName() override { return "GMSK"; }
+    int getDefaultSampleRate() override { return 19200; }                               // ModemGMSK.cpp:31-33
+    ModemArgInfoList getSettings() override {                                          // ModemGMSK.cpp:35-68
+        ModemArgInfoList args;
+        ModemArgInfo f;
+        f.key = "fdelay"; f.name = "Filter delay"; f.value = std::to_string(fdelay_.load()); f.description = "Filter delay in samples";
+        f.type = ModemArgInfo::Type::INT; f.units = "samples"; f.range = ModemRange(1, 128);
+        args.push_back(f);
+        ModemArgInfo s;
+        s.key = "sps"; s.name = "Samples / symbol"; s.value = std::to_string(sps_.load()); s.description = "Modem samples-per-symbol";
+        s.type = ModemArgInfo::Type::INT; s.units = "samples/symbol"; s.range = ModemRange(2, 512);
+        args.push_back(s);
+        ModemArgInfo e;
+        e.key = "ebf"; e.name = "Excess bandwidth"; e.value = std::to_string(ebf_.load()); e.description = "Modem excess bandwidth factor";
+        e.type = ModemArgInfo::Type::FLOAT; e.range = ModemRange(0.1, 0.49);
+        args.push_back(e);
+        return args;
+    }
+    void writeSetting(std::string setting, std::string value) override {               // ModemGMSK.cpp:70-81
+        if (setting == "fdelay") { fdelay_.store(std::stoi(value)); rebuildKit(); }
+        else if (setting == "sps") { sps_.store(std::stoi(value)); rebuildKit(); }
+        else if (setting == "ebf") { ebf_.store(std::stof(value)); rebuildKit(); }
+    }
+    std::string readSetting(std::string setting) override {
+        if (setting == "fdelay") return std::to_string(fdelay_.load());
+        if (setting == "sps") return std::to_string(sps_.load());
+        if (setting == "ebf") return std::to_string(ebf_.load());
+        return "";
+    }
+    csdr_digital_params csdrDigitalParams() override {
+        csdr_digital_params p{};
+        p.kind = CSDR_DIGITAL_GMSK; p.sps = sps_.load(); p.fdelay = fdelay_.load(); p.bw = ebf_.load();
+        return p;
+    }
+
+private:
+    std::atomic<int> sps_{4}, fdelay_{3};                                                  // ModemGMSK.cpp:7-10
+    std::atomic<float> ebf_{0.3f};
+};
+
+// GMSK is registered on its own (CubicSDR.cpp:321 registers it beside the others): registerDigitalLab's list stays the one it was
+inline void Modem::registerDigitalGMSK() {
+    registerBuiltins();
+    static std::once_flag once;
+    std::call_once(once, [] { addModemFactory(ModemGMSK::factory, "GMSK", 19200); });
+}
 
 inline void Modem::registerDigitalLab() {                                               // CubicSDR.cpp:315-328 (the built ones)
     registerBuiltins();

@@ -20,6 +20,7 @@
 #ifndef CSDR_HIP_H
 #define CSDR_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -228,7 +229,9 @@ int  csdr_bank_total_audio(csdr_bank *bank, int64_t *n);
  * A digital slot runs DemodulatorPreThread's arithmetic (NCO shift + msresamp_crcf to the modem rate, as any slot) and then the modem's
  * hard decisions: one per resampled IQ sample for the modemcf constellations (ModemPSK.cpp:108-118 and alike: no symbol timing), one per
  * k = rate / sps samples for FSK (ModemFSK.cpp:127-143, the samples short of a symbol carried to the next block).  No audio: n_audio, level
- * and peak of its csdr_block_result stay 0.  Not built: APSK, SQAM, V.29 (ModemST) and GMSK. */
+ * and peak of its csdr_block_result stay 0.  GMSK (ModemGMSK.cpp:116-134) runs gmskdem per sps samples of each block as the reference frames them:
+ * I = ceil((c + n) / sps / sps) symbols from the block's start, c = kit->inputBuffer.size() (samples past the block's end read as zero).
+ * Not built: APSK, SQAM and V.29 (ModemST), whose point tables are liquid's own. */
 #define CSDR_MODEM_DIGITAL 10        /* configured only through csdr_bank_configure_digital_slot */
 #define CSDR_DIGITAL_PSK   0         /* ModemPSK   modemcf PSK2..PSK256, lock at EVM <= 0.005 */
 #define CSDR_DIGITAL_DPSK  1         /* ModemDPSK  modemcf DPSK2..DPSK256, 0.005 */
@@ -238,14 +241,16 @@ int  csdr_bank_total_audio(csdr_bank *bank, int64_t *n);
 #define CSDR_DIGITAL_QPSK  5         /* ModemQPSK, 0.8 */
 #define CSDR_DIGITAL_OOK   6         /* ModemOOK, 0.005 */
 #define CSDR_DIGITAL_FSK   7         /* ModemFSK   fskdem(bps, rate / sps, bw); no lock (the reference never updates it) */
+#define CSDR_DIGITAL_GMSK  8         /* ModemGMSK  gmskdem(sps, fdelay, ebf); no lock; cons reported as 2 */
 
 typedef struct csdr_digital_params {
     int32_t kind;              /* CSDR_DIGITAL_* (the reference class) */
     int32_t cons;              /* PSK / DPSK / ASK: 2..256, QAM: 4..256, a power of two ("cons" setting); 0 = the reference default (2; QAM 4) */
     int32_t bps;               /* FSK bits per symbol ("bps"; 0 = 1) */
-    int32_t sps;               /* FSK symbols per second ("sps"; 0 = 9600) */
-    float   bw;                /* FSK signal bandwidth as a fraction of the modem rate ("bw"; 0 = 0.45) */
-    int32_t reserved[3];       /* 0 */
+    int32_t sps;               /* FSK symbols per second ("sps"; 0 = 9600).  GMSK: SAMPLES per symbol ("sps", 2..512; 0 = 4) -- not FSK's meaning */
+    float   bw;                /* FSK signal bandwidth as a fraction of the modem rate ("bw"; 0 = 0.45).  GMSK: the BT product ("ebf"; 0 = 0.3) */
+    int32_t fdelay;            /* GMSK filter delay in symbols ("fdelay", 1..128; 0 = 3); else 0 */
+    int32_t reserved[2];       /* 0 */
 } csdr_digital_params;
 
 /* per (digital slot, block) of the last execute */
@@ -255,7 +260,8 @@ typedef struct csdr_digital_result {
     int32_t lock;              /* updateDemodulatorLock after the block (ModemDigital.cpp:51-53): evm <= the modem's sensitivity; FSK: 0 */
     float   evm;               /* modemcf_get_demodulator_evm after the block: |x_hat - r| of the last decided sample (a block without samples
                                   repeats the previous value); FSK: 0 */
-    int32_t carry;             /* FSK: samples held for the next symbol after the block (kit->inputBuffer.size()); else 0 */
+    int32_t carry;             /* FSK: samples held for the next symbol after the block (kit->inputBuffer.size()); GMSK: the same count, which can
+                                  grow far above sps (ModemGMSK never reads those samples); else 0 */
     int32_t cons;              /* the constellation size the block was decided with (FSK: 2^bps; BPSK / QPSK / OOK: 2, 4, 2) */
     int32_t reserved[2];
 } csdr_digital_result;
@@ -287,6 +293,31 @@ int  csdr_bank_fetch_symbols(csdr_bank *bank, int slot, uint32_t *host_out, int 
  * constellation, whole symbols for FSK), *evm_last is the object's EVM afterwards (FSK: 0). */
 int  csdr_digital_run(csdr_ctx *ctx, const csdr_digital_params *d, int64_t sample_rate, const float *iq_host, int n, csdr_digital_state *state,
                       uint32_t *sym_host, int cap_symbols, int *n_symbols, float *evm_last);
+
+/* GMSK object state for csdr_gmsk_run (zero = freshly created); the filter window travels beside it in a caller-owned history of
+ * 2 sps fdelay floats (the last phase differences pushed, oldest first; zeros when fresh) */
+typedef struct csdr_gmsk_state {
+    float   x_prime[2];        /* the last sample demodulated */
+    int32_t reserved[2];
+} csdr_gmsk_state;
+
+/* The GMSK kernels alone on n caller-supplied samples (a multiple of sps): n / sps consecutive gmskdem_demodulate calls of one object whose state
+ * is *state and history (read, then updated); for parity checks on identical input.  Decisions go to sym_host, the receive filter's outputs they
+ * were taken from to soft_host (may be NULL); *n_symbols = n / sps.  CSDR_EUNSUPPORTED where csdr_bank_configure_digital_slot refuses. */
+int  csdr_gmsk_run(csdr_ctx *ctx, const csdr_digital_params *d, const float *iq_host, int n, csdr_gmsk_state *state, float *history,
+                   uint32_t *sym_host, float *soft_host, int cap_symbols, int *n_symbols);
+
+#ifdef __cplusplus
+#define CSDR_STATIC_ASSERT(c, m) static_assert(c, m)
+#else
+#define CSDR_STATIC_ASSERT(c, m) _Static_assert(c, m)
+#endif
+/* the digital lab's structures keep their layout */
+CSDR_STATIC_ASSERT(sizeof(csdr_digital_params) == 32 && offsetof(csdr_digital_params, bw) == 16 && offsetof(csdr_digital_params, fdelay) == 20,
+                   "csdr_digital_params layout");
+CSDR_STATIC_ASSERT(sizeof(csdr_digital_result) == 32 && offsetof(csdr_digital_result, carry) == 16, "csdr_digital_result layout");
+CSDR_STATIC_ASSERT(sizeof(csdr_digital_state) == 32 + 8 * CSDR_DIGITAL_MAX_CARRY && offsetof(csdr_digital_state, carry) == 32, "csdr_digital_state layout");
+CSDR_STATIC_ASSERT(sizeof(csdr_gmsk_state) == 16, "csdr_gmsk_state layout");
 
 /* ------------------------------------------------------------------ SpectrumVisualProcessor (src/process/SpectrumVisualProcessor.cpp)
  * replaces: setup :140-178 (fft_create_plan(2*fftSize, FORWARD)), process :212-637 full-span view:
