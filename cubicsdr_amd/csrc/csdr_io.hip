@@ -3,6 +3,7 @@
 //   csdr_mix     AudioThread's mixing callback                          (src/audio/AudioThread.cpp:88-240)
 //   PCM16        AudioFileWAV's payload conversion                      (src/audio/AudioFileWAV.cpp:133-157)
 //   csdr_ingest  SDRThread's block buffers -> HBM, one transfer per block (src/sdr/SoapySDRThread.cpp:221-225, :258-266; SDRPostThread.cpp:227-245)
+//                and the widening of the radio's native sample format on the GPU (:88-90 asks the driver for "CF32" instead)
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -503,17 +504,63 @@ struct csdr_ingest {
     int depth = 0, next = 0, acquired = -1;
     int64_t cap = 0;
     hipStream_t copy = nullptr;
-    std::vector<float2 *> host, dev;
+    std::vector<float2 *> host, dev;                                     // (a raw ingest's host slots hold slot_bytes of the radio's format)
     std::vector<hipEvent_t> ev_copied;                                   // slot's transfer finished
     std::vector<std::vector<hipEvent_t>> ev_done;                        // [slot][physical stream]: its consumers enqueued up to the next commit
     std::vector<char> copied_valid, done_valid;
+    // native sample formats (csdr_ingest_create_raw)
+    bool raw = false;
+    csdr_iq_format fmt{};                                                // of the next commit / upload
+    uint64_t slot_bytes = 0;                                             // of one page-locked slot: the format the ring was created for
+    DevBuf<unsigned char> stage;                                         // the raw bytes in HBM, between the DMA and the conversion (first use)
 };
 extern "C" void csdr_ingest_destroy(csdr_ingest *g);
-extern "C" int csdr_ingest_create(csdr_ctx *ctx, int64_t max_samples, int depth, csdr_ingest **out) {
-    DeviceScope dev__(ctx);
-    if (!ctx || !out || max_samples <= 0 || depth < 2 || depth > 16) return fail(CSDR_EINVAL, "bad argument (depth 2..16)");
+
+static int iq_sample_bytes(int format) {
+    switch (format) {
+    case CSDR_IQ_CF32: return 8;
+    case CSDR_IQ_CS16: return 4;
+    case CSDR_IQ_CS8: case CSDR_IQ_CU8: return 2;
+    case CSDR_IQ_CS12: return 3;
+    default: return 0;
+    }
+}
+static int iq_format_check(const csdr_iq_format *f) {
+    if (!f) return fail(CSDR_EINVAL, "format is null");
+    if (!iq_sample_bytes(f->format)) return fail(CSDR_EINVAL, "unknown sample format %d", (int)f->format);
+    if (f->format == CSDR_IQ_CF32) return CSDR_OK;                                    // no conversion: nothing else is read
+    if (!std::isfinite(f->full_scale) || !(f->full_scale > 0.0)) return fail(CSDR_EINVAL, "full_scale must be finite and positive");
+    if (!std::isfinite(f->offset)) return fail(CSDR_EINVAL, "offset must be finite");
+    if (f->format != CSDR_IQ_CU8 && f->offset != 0.0f) return fail(CSDR_EINVAL, "a signed format takes no offset");
+    return CSDR_OK;
+}
+extern "C" int csdr_iq_format_bytes(int format, int64_t n_samples, uint64_t *bytes) {
+    const int b = iq_sample_bytes(format);
+    if (!b || n_samples < 0 || !bytes) return fail(CSDR_EINVAL, "bad argument");
+    *bytes = (uint64_t)n_samples * (uint64_t)b;
+    return CSDR_OK;
+}
+// raw samples (device-visible, 16-byte aligned) -> CF32 in HBM, on `st`
+static int iq_convert_launch(csdr_ctx *c, hipStream_t st, const csdr_iq_format &f, const void *raw, float2 *dst, int64_t n, int iq_swap) {
+    const float s = (float)(1.0 / f.full_scale);
+    const int64_t groups = n / iq_group(f.format);
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(4 * c->n_cu, (groups + 255) / 256));
+    switch (f.format) {
+    case CSDR_IQ_CS16: hipLaunchKernelGGL(ingest_convert<CSDR_IQ_CS16>, dim3((unsigned)grid), dim3(256), 0, st, raw, dst, n, f.offset, s, iq_swap); break;
+    case CSDR_IQ_CS8: hipLaunchKernelGGL(ingest_convert<CSDR_IQ_CS8>, dim3((unsigned)grid), dim3(256), 0, st, raw, dst, n, f.offset, s, iq_swap); break;
+    case CSDR_IQ_CU8: hipLaunchKernelGGL(ingest_convert<CSDR_IQ_CU8>, dim3((unsigned)grid), dim3(256), 0, st, raw, dst, n, f.offset, s, iq_swap); break;
+    case CSDR_IQ_CS12: hipLaunchKernelGGL(ingest_convert<CSDR_IQ_CS12>, dim3((unsigned)grid), dim3(256), 0, st, raw, dst, n, f.offset, s, iq_swap); break;
+    default: return fail(CSDR_EINVAL, "no conversion for format %d", (int)f.format);
+    }
+    CSDR_HIP_TRY(hipGetLastError());
+    return CSDR_OK;
+}
+
+static int ingest_build(csdr_ctx *ctx, int64_t max_samples, int depth, const csdr_iq_format *fmt, csdr_ingest **out) {
     csdr_ingest *g = new csdr_ingest();
     g->ctx = ctx; g->depth = depth; g->cap = max_samples;
+    g->slot_bytes = (uint64_t)max_samples * sizeof(float2);
+    if (fmt) { g->raw = true; g->fmt = *fmt; g->slot_bytes = (uint64_t)max_samples * (uint64_t)iq_sample_bytes(fmt->format); }
     g->host.assign((size_t)depth, nullptr); g->dev.assign((size_t)depth, nullptr);
     g->ev_copied.assign((size_t)depth, nullptr); g->ev_done.assign((size_t)depth, std::vector<hipEvent_t>());
     g->copied_valid.assign((size_t)depth, 0); g->done_valid.assign((size_t)depth, 0);
@@ -521,7 +568,7 @@ extern "C" int csdr_ingest_create(csdr_ctx *ctx, int64_t max_samples, int depth,
     auto build = [&]() -> int {
         CSDR_HIP_TRY(hipStreamCreateWithFlags(&g->copy, hipStreamNonBlocking));
         for (int k = 0; k < depth; ++k) {
-            if (hipHostMalloc((void **)&g->host[(size_t)k], (size_t)max_samples * sizeof(float2), hipHostMallocDefault) != hipSuccess) return fail(CSDR_ENOMEM, "pinned ingest slot of %lld samples", (long long)max_samples);
+            if (hipHostMalloc((void **)&g->host[(size_t)k], (size_t)g->slot_bytes, hipHostMallocDefault) != hipSuccess) return fail(CSDR_ENOMEM, "pinned ingest slot of %lld samples", (long long)max_samples);
             if (hipMalloc((void **)&g->dev[(size_t)k], (size_t)max_samples * sizeof(float2)) != hipSuccess) return fail(CSDR_ENOMEM, "device ingest slot");
             CSDR_HIP_TRY(hipEventCreateWithFlags(&g->ev_copied[(size_t)k], hipEventDisableTiming));
             g->ev_done[(size_t)k].assign((size_t)ctx->n_phys + 1, nullptr);
@@ -532,6 +579,17 @@ extern "C" int csdr_ingest_create(csdr_ctx *ctx, int64_t max_samples, int depth,
     if (int rc = build()) { const std::string why = last_error_ref(); csdr_ingest_destroy(g); last_error_ref() = why; return rc; }
     *out = g;
     return CSDR_OK;
+}
+extern "C" int csdr_ingest_create(csdr_ctx *ctx, int64_t max_samples, int depth, csdr_ingest **out) {
+    DeviceScope dev__(ctx);
+    if (!ctx || !out || max_samples <= 0 || depth < 2 || depth > 16) return fail(CSDR_EINVAL, "bad argument (depth 2..16)");
+    return ingest_build(ctx, max_samples, depth, nullptr, out);
+}
+extern "C" int csdr_ingest_create_raw(csdr_ctx *ctx, int64_t max_samples, int depth, const csdr_iq_format *fmt, csdr_ingest **out) {
+    DeviceScope dev__(ctx);
+    if (!ctx || !out || max_samples <= 0 || depth < 2 || depth > 16) return fail(CSDR_EINVAL, "bad argument (depth 2..16)");
+    if (int rc = iq_format_check(fmt)) return rc;
+    return ingest_build(ctx, max_samples, depth, fmt, out);
 }
 extern "C" void csdr_ingest_destroy(csdr_ingest *g) {
     DeviceScope dev__(g ? g->ctx : nullptr);
@@ -544,20 +602,34 @@ extern "C" void csdr_ingest_destroy(csdr_ingest *g) {
         if (g->ev_copied[(size_t)k]) (void)hipEventDestroy(g->ev_copied[(size_t)k]);
         for (auto &e : g->ev_done[(size_t)k]) if (e) (void)hipEventDestroy(e);
     }
+    g->stage.release();
     delete g;
 }
-// the page-locked slot the next batch is assembled in; waits until the transfer that last read this slot is over
-extern "C" int csdr_ingest_acquire(csdr_ingest *g, float **host_slot) {
-    DeviceScope dev__(g ? g->ctx : nullptr);
-    if (!g || !host_slot) return fail(CSDR_EINVAL, "bad argument");
+// the slot the next block is assembled in; waits until the transfer that last read this slot is over
+static int ingest_acquire(csdr_ingest *g, void **host_slot) {
     const int k = g->next;
     if (g->copied_valid[(size_t)k]) CSDR_HIP_TRY(hipEventSynchronize(g->ev_copied[(size_t)k]));
     g->acquired = k;
-    *host_slot = (float *)g->host[(size_t)k];
+    *host_slot = g->host[(size_t)k];
     return CSDR_OK;
 }
-// the transfer of slot k from `src` (its own page-locked twin, or caller memory), ordered against the slot's previous consumers
-static int ingest_transfer(csdr_ingest *g, int k, const float2 *src, bool src_is_slot, int64_t n_samples, int iq_swap, const float **dev_iq) {
+// the page-locked slot the next batch is assembled in
+extern "C" int csdr_ingest_acquire(csdr_ingest *g, float **host_slot) {
+    DeviceScope dev__(g ? g->ctx : nullptr);
+    if (!g || !host_slot) return fail(CSDR_EINVAL, "bad argument");
+    if (g->raw) return fail(CSDR_ESTATE, "a raw ingest: csdr_ingest_acquire_raw");
+    return ingest_acquire(g, (void **)host_slot);
+}
+extern "C" int csdr_ingest_acquire_raw(csdr_ingest *g, void **host_slot) {
+    DeviceScope dev__(g ? g->ctx : nullptr);
+    if (!g || !host_slot) return fail(CSDR_EINVAL, "bad argument");
+    if (!g->raw) return fail(CSDR_ESTATE, "not a raw ingest: csdr_ingest_acquire");
+    return ingest_acquire(g, host_slot);
+}
+// The transfer into HBM slot k, ordered against the slot's previous consumers in front and the consumers to come behind; `move` enqueues on
+// g->copy whatever brings the block into g->dev[k] (a DMA, the exchanging kernel, a format conversion).
+template <typename Move>
+static int ingest_transfer(csdr_ingest *g, int k, const float **dev_iq, Move &&move) {
     csdr_ctx *c = g->ctx;
     const int prev = (k + g->depth - 1) % g->depth;
     // everything enqueued so far may still read the PREVIOUS slot's device copy: mark it (one event per stream that can hold consumers)
@@ -568,6 +640,19 @@ static int ingest_transfer(csdr_ingest *g, int k, const float2 *src, bool src_is
     }
     // the device twin of THIS slot was last read by the consumers of `depth` transfers ago
     if (g->done_valid[(size_t)k]) for (auto &e : g->ev_done[(size_t)k]) CSDR_HIP_TRY(hipStreamWaitEvent(g->copy, e, 0));
+    if (int rc = move()) return rc;
+    CSDR_HIP_TRY(hipEventRecord(g->ev_copied[(size_t)k], g->copy));
+    g->copied_valid[(size_t)k] = 1;
+    // consumers on any of the library's streams (and on the boundary stream) start behind the transfer
+    for (int l = 0; l < c->n_phys; ++l) CSDR_HIP_TRY(hipStreamWaitEvent(c->phys[l], g->ev_copied[(size_t)k], 0));
+    if (!c->own_stream) CSDR_HIP_TRY(hipStreamWaitEvent(c->stream, g->ev_copied[(size_t)k], 0));
+    *dev_iq = (const float *)g->dev[(size_t)k];
+    g->next = (k + 1) % g->depth;
+    return CSDR_OK;
+}
+// CF32 from `src` (the slot's own page-locked twin, or caller memory)
+static int ingest_move_cf32(csdr_ingest *g, int k, const float2 *src, bool src_is_slot, int64_t n_samples, int iq_swap) {
+    csdr_ctx *c = g->ctx;
     const int grid = std::max(1, std::min(4 * c->n_cu, (int)((n_samples + 255) / 256)));
     if (iq_swap && src_is_slot) {
         // the slot is mapped into the device's address space: the exchanging kernel IS the transfer
@@ -580,23 +665,49 @@ static int ingest_transfer(csdr_ingest *g, int k, const float2 *src, bool src_is
             CSDR_HIP_TRY(hipGetLastError());
         }
     }
-    CSDR_HIP_TRY(hipEventRecord(g->ev_copied[(size_t)k], g->copy));
-    g->copied_valid[(size_t)k] = 1;
-    // consumers on any of the library's streams (and on the boundary stream) start behind the transfer
-    for (int l = 0; l < c->n_phys; ++l) CSDR_HIP_TRY(hipStreamWaitEvent(c->phys[l], g->ev_copied[(size_t)k], 0));
-    if (!c->own_stream) CSDR_HIP_TRY(hipStreamWaitEvent(c->stream, g->ev_copied[(size_t)k], 0));
-    *dev_iq = (const float *)g->dev[(size_t)k];
-    g->next = (k + 1) % g->depth;
     return CSDR_OK;
+}
+// The radio's format from `src` (the slot's own page-locked twin, or caller memory): ONE DMA of the raw bytes into the staging buffer, the
+// conversion in HBM behind it.  Letting the converting kernel read the mapped slot over the link (the kernel as the transfer, as ingest_swap
+// does) was measured against this: alone it moves CS16 / CS8 at 13.1 / 25.6 GS/s against 13.0 / 23.7, but beside the C3 pipeline -- the case
+// the ring exists for -- a kernel that holds its waves for a millisecond of link time gives 11.5 / 19.8 GS/s against 12.3 / 21.5 for the DMA
+// engine plus 40 - 60 us of conversion (profiles/host_fed_formats.txt).  The staging buffer is shared by the slots: every
+// transfer of this ingest runs on g->copy, in order.
+static int ingest_move_raw(csdr_ingest *g, int k, const void *src, bool src_is_slot, int64_t n_samples, int iq_swap) {
+    if (g->fmt.format == CSDR_IQ_CF32) return ingest_move_cf32(g, k, (const float2 *)src, src_is_slot, n_samples, iq_swap);
+    const size_t bytes = (size_t)n_samples * (size_t)iq_sample_bytes(g->fmt.format);
+    CSDR_HIP_TRY(hipMemcpyAsync(g->stage.p, src, bytes, hipMemcpyHostToDevice, g->copy));
+    return iq_convert_launch(g->ctx, g->copy, g->fmt, g->stage.p, g->dev[(size_t)k], n_samples, iq_swap);
 }
 extern "C" int csdr_ingest_commit(csdr_ingest *g, int64_t n_samples, int iq_swap, const float **dev_iq) {
     DeviceScope dev__(g ? g->ctx : nullptr);
     if (!g || !dev_iq) return fail(CSDR_EINVAL, "bad argument");
+    if (g->raw) return fail(CSDR_ESTATE, "a raw ingest: csdr_ingest_commit_raw");
     if (g->acquired < 0) return fail(CSDR_ESTATE, "commit without acquire");
     if (n_samples <= 0 || n_samples > g->cap) return fail(CSDR_ERANGE, "%lld samples (slot holds %lld)", (long long)n_samples, (long long)g->cap);
     const int k = g->acquired;
     g->acquired = -1;
-    return ingest_transfer(g, k, g->host[(size_t)k], true, n_samples, iq_swap, dev_iq);
+    return ingest_transfer(g, k, dev_iq, [&]() { return ingest_move_cf32(g, k, g->host[(size_t)k], true, n_samples, iq_swap); });
+}
+extern "C" int csdr_ingest_commit_raw(csdr_ingest *g, int64_t n_samples, int iq_swap, const float **dev_iq) {
+    DeviceScope dev__(g ? g->ctx : nullptr);
+    if (!g || !dev_iq) return fail(CSDR_EINVAL, "bad argument");
+    if (!g->raw) return fail(CSDR_ESTATE, "not a raw ingest: csdr_ingest_commit");
+    if (g->acquired < 0) return fail(CSDR_ESTATE, "commit without acquire");
+    if (n_samples <= 0 || n_samples > g->cap) return fail(CSDR_ERANGE, "%lld samples (slot holds %lld)", (long long)n_samples, (long long)g->cap);
+    if (g->fmt.format != CSDR_IQ_CF32) if (int rc = g->stage.reserve((size_t)g->slot_bytes)) return rc;
+    const int k = g->acquired;
+    g->acquired = -1;
+    return ingest_transfer(g, k, dev_iq, [&]() { return ingest_move_raw(g, k, g->host[(size_t)k], true, n_samples, iq_swap); });
+}
+extern "C" int csdr_ingest_set_format(csdr_ingest *g, const csdr_iq_format *fmt) {
+    if (!g) return fail(CSDR_EINVAL, "ingest is null");
+    if (!g->raw) return fail(CSDR_ESTATE, "not a raw ingest");
+    if (int rc = iq_format_check(fmt)) return rc;
+    // a slot keeps holding `cap` samples, so n_samples is checked against one capacity whatever the format
+    if ((uint64_t)iq_sample_bytes(fmt->format) * (uint64_t)g->cap > g->slot_bytes) return fail(CSDR_EINVAL, "format %d has larger samples than the ring was created for", (int)fmt->format);
+    g->fmt = *fmt;
+    return CSDR_OK;
 }
 // blocks until the last transfer has left its source buffer (a caller that is about to rewrite or recycle the block it just uploaded)
 extern "C" int csdr_ingest_wait(csdr_ingest *g) {
@@ -615,8 +726,56 @@ extern "C" int csdr_ingest_upload(csdr_ingest *g, const float *host_iq, int64_t 
     RangeScope range__("csdr_ingest_upload");
     DeviceScope dev__(g ? g->ctx : nullptr);
     if (!g || !host_iq || !dev_iq) return fail(CSDR_EINVAL, "bad argument");
+    if (g->raw) return fail(CSDR_ESTATE, "a raw ingest: csdr_ingest_upload_raw");
     if (n_samples <= 0 || n_samples > g->cap) return fail(CSDR_ERANGE, "%lld samples (slot holds %lld)", (long long)n_samples, (long long)g->cap);
     const int k = g->next, prev = (k + g->depth - 1) % g->depth;
     if (g->copied_valid[(size_t)prev]) CSDR_HIP_TRY(hipEventSynchronize(g->ev_copied[(size_t)prev]));
-    return ingest_transfer(g, k, (const float2 *)host_iq, false, n_samples, iq_swap, dev_iq);
+    return ingest_transfer(g, k, dev_iq, [&]() { return ingest_move_cf32(g, k, (const float2 *)host_iq, false, n_samples, iq_swap); });
+}
+// the same for a block in the radio's format: the raw bytes cross the link by DMA into the ingest's staging buffer, the conversion runs in HBM
+extern "C" int csdr_ingest_upload_raw(csdr_ingest *g, const void *host_raw, int64_t n_samples, int iq_swap, const float **dev_iq) {
+    RangeScope range__("csdr_ingest_upload_raw");
+    DeviceScope dev__(g ? g->ctx : nullptr);
+    if (!g || !host_raw || !dev_iq) return fail(CSDR_EINVAL, "bad argument");
+    if (!g->raw) return fail(CSDR_ESTATE, "not a raw ingest: csdr_ingest_upload");
+    if (n_samples <= 0 || n_samples > g->cap) return fail(CSDR_ERANGE, "%lld samples (slot holds %lld)", (long long)n_samples, (long long)g->cap);
+    const int k = g->next, prev = (k + g->depth - 1) % g->depth;
+    // (the previous upload is the staging buffer's last reader, too)
+    if (g->copied_valid[(size_t)prev]) CSDR_HIP_TRY(hipEventSynchronize(g->ev_copied[(size_t)prev]));
+    if (g->fmt.format != CSDR_IQ_CF32) if (int rc = g->stage.reserve((size_t)g->slot_bytes)) return rc;
+    return ingest_transfer(g, k, dev_iq, [&]() { return ingest_move_raw(g, k, host_raw, false, n_samples, iq_swap); });
+}
+
+// The conversion kernel alone on caller-supplied samples (parity checks on identical input): staged into HBM, converted, fetched.  The device
+// output carries a guard band that is read back with it: a kernel that wrote past its n_samples fails the call.
+extern "C" int csdr_iq_convert(csdr_ctx *ctx, const csdr_iq_format *fmt, const void *raw_host, int64_t n_samples, int iq_swap, float *out_host) {
+    DeviceScope dev__(ctx);
+    if (!ctx || !raw_host || !out_host || n_samples <= 0) return fail(CSDR_EINVAL, "bad argument");
+    if (int rc = iq_format_check(fmt)) return rc;
+    const size_t bytes = (size_t)n_samples * (size_t)iq_sample_bytes(fmt->format);
+    if (fmt->format == CSDR_IQ_CF32 && !iq_swap) { std::memcpy(out_host, raw_host, bytes); return CSDR_OK; }
+    hipStream_t st = ctx->stream;
+    DevBuf<unsigned char> in;
+    DevBuf<float2> out;
+    constexpr size_t kGuard = 32;                                                     // samples behind the output that must stay as they were
+    unsigned char guard[kGuard * sizeof(float2)];
+    auto run = [&]() -> int {
+        if (int rc = in.reserve(bytes)) return rc;
+        if (int rc = out.reserve((size_t)n_samples + kGuard)) return rc;
+        CSDR_HIP_TRY(hipMemsetAsync(out.p + n_samples, 0x5A, kGuard * sizeof(float2), st));
+        CSDR_HIP_TRY(hipMemcpyAsync(in.p, raw_host, bytes, hipMemcpyHostToDevice, st));
+        if (fmt->format == CSDR_IQ_CF32) {
+            hipLaunchKernelGGL(ingest_swap, dim3((unsigned)std::max(1, std::min(4 * ctx->n_cu, (int)((n_samples + 255) / 256)))), dim3(256), 0, st, (const float2 *)in.p, out.p, n_samples);
+            CSDR_HIP_TRY(hipGetLastError());
+        } else if (int rc = iq_convert_launch(ctx, st, *fmt, in.p, out.p, n_samples, iq_swap)) return rc;
+        CSDR_HIP_TRY(hipMemcpyAsync(out_host, out.p, (size_t)n_samples * sizeof(float2), hipMemcpyDeviceToHost, st));
+        CSDR_HIP_TRY(hipMemcpyAsync(guard, out.p + n_samples, sizeof guard, hipMemcpyDeviceToHost, st));
+        CSDR_HIP_TRY(hipStreamSynchronize(st));
+        for (unsigned char b : guard) if (b != 0x5A) return fail(CSDR_EHIP, "the conversion wrote past its %lld output samples", (long long)n_samples);
+        return CSDR_OK;
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(st);
+    in.release(); out.release();
+    return rc;
 }

@@ -1,4 +1,4 @@
-// kernels_io.hpp -- the edges of the hot path on the GPU: audio scope, audio mix-down, PCM conversion, ingest swap.
+// kernels_io.hpp -- the edges of the hot path on the GPU: audio scope, audio mix-down, PCM conversion, ingest swap, ingest format conversion.
 //
 // Replaces the arithmetic of (reference file:line):
 //   ScopeVisualProcessor::process      src/process/ScopeVisualProcessor.cpp:45-217   (waveform normalisation :64-117, audio FFT +
@@ -6,6 +6,7 @@
 //   audioCallback                      src/audio/AudioThread.cpp:88-240              (per-source gain, mono fan-out, sum, peak normalisation)
 //   AudioFileWAV::writePayloadToFileStream  src/audio/AudioFileWAV.cpp:133-157       (anti-clipping scale, float -> int16)
 //   SDRThread::readStream IQ swap      src/sdr/SoapySDRThread.cpp:258-266, :300-308  (applied while the block crosses the link)
+//   the driver's widening to "CF32"    src/sdr/SoapySDRThread.cpp:88-90              (the stream is opened in the radio's own format instead; ingest_convert)
 // Host control flow (which block is current, queue rules, file headers) lives in csdr_io.hip; only arithmetic is here.
 // All LDS is dynamic (`smem`).
 #pragma once
@@ -249,6 +250,87 @@ CSDR_KERNEL __launch_bounds__(256) void ingest_swap(const float2 *src, float2 *d
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)256 * gridDim.x) {
         const float2 v = src[i];
         dst[i] = make_float2(v.y, v.x);
+    }
+}
+
+// ---- ingest: the radio's own sample format -> CF32 (csdr_hip.h, "native sample formats").  Every component is
+//     y = ((float)x - offset) * s,  s = (float)(1.0 / full_scale) rounded once on the host,
+// the difference and the product each rounded once in float32 ((float)x is exact for 8, 12 and 16 bits); with `swap` the two converted
+// components change places.  Pure streaming: a lane takes 16 bytes of raw samples per load (48 bytes = three loads for the packed 12-bit
+// format, whose samples would otherwise straddle lanes) and writes them as float4; the last partial group goes sample by sample.
+// `raw` and `dst` are 16-byte aligned (the library's own allocations): `raw` is the ingest's staging buffer in HBM, which the raw bytes
+// reached by DMA -- the link carries 2 - 4 bytes per sample instead of 8.  (It also runs on a page-locked host slot mapped into the device's
+// address space, at the link's rate; csdr_io.hip says why that is not the shipped path.)
+__device__ __forceinline__ float iq_value(int x, float offset, float s) { return rounded(rounded((float)x - offset) * s); }
+__device__ __forceinline__ float4 iq_two(int i0, int q0, int i1, int q1, float offset, float s, bool swap) {
+    const float a = iq_value(i0, offset, s), b = iq_value(q0, offset, s), c = iq_value(i1, offset, s), d = iq_value(q1, offset, s);
+    return swap ? make_float4(b, a, d, c) : make_float4(a, b, c, d);
+}
+__device__ __forceinline__ int iq_lo16(int w) { return (int)(short)(w & 0xffff); }
+__device__ __forceinline__ int iq_hi16(int w) { return w >> 16; }
+template <int FMT> __device__ __forceinline__ int iq_byte(int w, int k) {                 // byte k of a word as the format reads it
+    const int b = (int)(((unsigned)w >> (8 * k)) & 0xffu);
+    return FMT == CSDR_IQ_CS8 ? (int)(signed char)b : b;
+}
+__device__ __forceinline__ int iq_i12(unsigned v) { return (int)(v << 20) >> 20; }        // v = b0 | b1 << 8 | b2 << 16: I = bits 0..11, Q = bits 12..23
+__device__ __forceinline__ int iq_q12(unsigned v) { return (int)(v << 8) >> 20; }
+template <int FMT> __device__ __forceinline__ float4 iq_word8(int w, float offset, float s, bool swap) {   // one word = two 8-bit samples
+    return iq_two(iq_byte<FMT>(w, 0), iq_byte<FMT>(w, 1), iq_byte<FMT>(w, 2), iq_byte<FMT>(w, 3), offset, s, swap);
+}
+// three words = four packed 12-bit samples -> out[0], out[1]
+__device__ __forceinline__ void iq_words12(unsigned w0, unsigned w1, unsigned w2, float offset, float s, bool swap, float4 *out) {
+    const unsigned s0 = w0 & 0xffffffu, s1 = (w0 >> 24) | ((w1 & 0xffffu) << 8), s2 = (w1 >> 16) | ((w2 & 0xffu) << 16), s3 = w2 >> 8;
+    out[0] = iq_two(iq_i12(s0), iq_q12(s0), iq_i12(s1), iq_q12(s1), offset, s, swap);
+    out[1] = iq_two(iq_i12(s2), iq_q12(s2), iq_i12(s3), iq_q12(s3), offset, s, swap);
+}
+constexpr int iq_group(int fmt) { return fmt == CSDR_IQ_CS16 ? 4 : fmt == CSDR_IQ_CS12 ? 16 : 8; }   // samples a lane converts per turn
+
+template <int FMT>
+CSDR_KERNEL __launch_bounds__(256) void ingest_convert(const void *__restrict__ raw, float2 *__restrict__ dst, int64_t n, float offset, float s, int iq_swap) {
+    constexpr int G = iq_group(FMT);
+    const bool swap = iq_swap != 0;
+    const int64_t groups = n / G;
+    const int4 *src = reinterpret_cast<const int4 *>(raw);
+    float4 *out = reinterpret_cast<float4 *>(dst);
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)256 * gridDim.x) {
+        if constexpr (FMT == CSDR_IQ_CS16) {
+            const int4 w = src[g];
+            out[2 * g] = iq_two(iq_lo16(w.x), iq_hi16(w.x), iq_lo16(w.y), iq_hi16(w.y), offset, s, swap);
+            out[2 * g + 1] = iq_two(iq_lo16(w.z), iq_hi16(w.z), iq_lo16(w.w), iq_hi16(w.w), offset, s, swap);
+        } else if constexpr (FMT == CSDR_IQ_CS12) {
+            const int4 a = src[3 * g], b = src[3 * g + 1], c = src[3 * g + 2];
+            float4 *o = out + 8 * g;
+            iq_words12((unsigned)a.x, (unsigned)a.y, (unsigned)a.z, offset, s, swap, o);
+            iq_words12((unsigned)a.w, (unsigned)b.x, (unsigned)b.y, offset, s, swap, o + 2);
+            iq_words12((unsigned)b.z, (unsigned)b.w, (unsigned)c.x, offset, s, swap, o + 4);
+            iq_words12((unsigned)c.y, (unsigned)c.z, (unsigned)c.w, offset, s, swap, o + 6);
+        } else {
+            const int4 w = src[g];
+            float4 *o = out + 4 * g;
+            o[0] = iq_word8<FMT>(w.x, offset, s, swap);
+            o[1] = iq_word8<FMT>(w.y, offset, s, swap);
+            o[2] = iq_word8<FMT>(w.z, offset, s, swap);
+            o[3] = iq_word8<FMT>(w.w, offset, s, swap);
+        }
+    }
+    // the last n % G samples, one per work-item
+    const int64_t t = groups * G + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < n) {
+        const unsigned char *p = reinterpret_cast<const unsigned char *>(raw);
+        int i, q;
+        if constexpr (FMT == CSDR_IQ_CS16) {
+            p += 4 * t;
+            i = (int)(short)(p[0] | (p[1] << 8)); q = (int)(short)(p[2] | (p[3] << 8));
+        } else if constexpr (FMT == CSDR_IQ_CS12) {
+            p += 3 * t;
+            const unsigned v = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+            i = iq_i12(v); q = iq_q12(v);
+        } else {
+            p += 2 * t;
+            i = FMT == CSDR_IQ_CS8 ? (int)(signed char)p[0] : (int)p[0]; q = FMT == CSDR_IQ_CS8 ? (int)(signed char)p[1] : (int)p[1];
+        }
+        const float a = iq_value(i, offset, s), b = iq_value(q, offset, s);
+        dst[t] = swap ? make_float2(b, a) : make_float2(a, b);
     }
 }
 

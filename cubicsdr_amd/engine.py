@@ -647,27 +647,97 @@ class Comm:
             self.h = C.c_void_p()
 
 
-class Ingest:
-    """page-locked block ring -> HBM, ONE transfer per block (csdr_ingest); commit returns the device pointer as an integer"""
+IQ_SAMPLE_BYTES = {H.CSDR_IQ_CF32: 8, H.CSDR_IQ_CS16: 4, H.CSDR_IQ_CS8: 2, H.CSDR_IQ_CU8: 2, H.CSDR_IQ_CS12: 3}
+_IQ_DTYPE = {H.CSDR_IQ_CF32: np.float32, H.CSDR_IQ_CS16: np.int16, H.CSDR_IQ_CS8: np.int8, H.CSDR_IQ_CU8: np.uint8, H.CSDR_IQ_CS12: np.uint8}
 
-    def __init__(self, ctx, max_samples, depth=3):
+
+def iq_format(format, full_scale=None, offset=0.0):
+    """-> H.IqFormat.  `format`: a name ("CS16", "CS8", "CU8", "CS12", "CF32") or a CSDR_IQ_* constant; full_scale as the radio reports it."""
+    f = H.IQ_FORMAT_BY_NAME[format] if isinstance(format, str) else int(format)
+    if full_scale is None:
+        if f != H.CSDR_IQ_CF32:
+            raise ValueError("full_scale is required for an integer sample format (what the radio reports: 32768, 2048, 128 ...)")
+        full_scale = 1.0                                      # unused: CF32 runs no conversion
+    return H.IqFormat(f, float(offset), float(full_scale))
+
+
+def pack_cs12(i, q):
+    """integer I / Q arrays (the low 12 bits of each are kept) -> the packed 12-bit stream, 3 bytes per sample:
+    b0 = I[7:0], b1 = Q[3:0] << 4 | I[11:8], b2 = Q[11:4]"""
+    i = np.asarray(i).astype(np.int64) & 0xFFF
+    q = np.asarray(q).astype(np.int64) & 0xFFF
+    out = np.empty((i.size, 3), np.uint8)
+    out[:, 0] = i & 0xFF
+    out[:, 1] = ((q & 0xF) << 4) | (i >> 8)
+    out[:, 2] = q >> 4
+    return out.reshape(-1)
+
+
+def iq_convert(ctx, raw, format, full_scale=None, offset=0.0, iq_swap=False, n_samples=None):
+    """csdr_iq_convert: the conversion kernel alone on `raw` (a contiguous numpy array holding whole samples of the format) -> complex64"""
+    f = iq_format(format, full_scale, offset)
+    a = np.ascontiguousarray(raw)
+    n = a.nbytes // IQ_SAMPLE_BYTES.get(f.format, 1) if n_samples is None else int(n_samples)
+    out = np.empty(max(1, n), np.complex64)
+    H.check(H.lib().csdr_iq_convert(ctx.h, C.byref(f), a.ctypes.data_as(C.c_void_p), n, int(iq_swap), out.ctypes.data_as(C.c_void_p)))
+    return out[:n]
+
+
+class Ingest:
+    """page-locked block ring -> HBM, ONE transfer per block (csdr_ingest); commit returns the device pointer as an integer.
+    With `format` (see iq_format) the slots hold the radio's own sample format and the block is widened to complex64 on the GPU."""
+
+    def __init__(self, ctx, max_samples, depth=3, format=None, full_scale=None, offset=0.0):
         self._l = H.lib()
         self.ctx = ctx
         self.h = C.c_void_p()
         self.max_samples = int(max_samples)
-        H.check(self._l.csdr_ingest_create(ctx.h, self.max_samples, int(depth), C.byref(self.h)))
+        self.format = None
+        if format is None:
+            H.check(self._l.csdr_ingest_create(ctx.h, self.max_samples, int(depth), C.byref(self.h)))
+        else:
+            f = iq_format(format, full_scale, offset)
+            H.check(self._l.csdr_ingest_create_raw(ctx.h, self.max_samples, int(depth), C.byref(f), C.byref(self.h)))
+            self.format = f
 
     def acquire(self):
-        """-> numpy complex64 view of the page-locked slot (max_samples long)"""
+        """-> numpy view of the page-locked slot (max_samples long): complex64, or with a format its integers -- int16 / int8 / uint8 [n, 2] pairs,
+        uint8 bytes (3 per sample) for CS12"""
         p = C.c_void_p()
-        H.check(self._l.csdr_ingest_acquire(self.h, C.byref(p)))
-        buf = (C.c_float * (2 * self.max_samples)).from_address(p.value)
-        return np.frombuffer(buf, dtype=np.complex64)
+        if self.format is None:
+            H.check(self._l.csdr_ingest_acquire(self.h, C.byref(p)))
+            buf = (C.c_float * (2 * self.max_samples)).from_address(p.value)
+            return np.frombuffer(buf, dtype=np.complex64)
+        H.check(self._l.csdr_ingest_acquire_raw(self.h, C.byref(p)))
+        fmt = self.format.format
+        buf = (C.c_ubyte * (IQ_SAMPLE_BYTES[fmt] * self.max_samples)).from_address(p.value)
+        a = np.frombuffer(buf, dtype=_IQ_DTYPE[fmt])
+        return a if fmt == H.CSDR_IQ_CS12 else a.reshape(-1, 2)
 
     def commit(self, n_samples, iq_swap=False):
         p = C.c_void_p()
-        H.check(self._l.csdr_ingest_commit(self.h, int(n_samples), int(iq_swap), C.byref(p)))
+        fn = self._l.csdr_ingest_commit if self.format is None else self._l.csdr_ingest_commit_raw
+        H.check(fn(self.h, int(n_samples), int(iq_swap), C.byref(p)))
         return DevicePointer(p.value, int(n_samples))
+
+    def upload_raw(self, raw, n_samples, iq_swap=False):
+        """a block of the current format in the caller's own memory (any alignment, pageable or registered) -> DevicePointer"""
+        p = C.c_void_p()
+        H.check(self._l.csdr_ingest_upload_raw(self.h, C.c_void_p(raw.ctypes.data), int(n_samples), int(iq_swap), C.byref(p)))
+        self._last_upload = raw                               # (the DMA may still read it: see wait())
+        return DevicePointer(p.value, int(n_samples))
+
+    def set_format(self, format, full_scale=None, offset=0.0):
+        """from the next commit / upload on (a format whose samples are no larger than those the ring was created for)"""
+        f = iq_format(format, full_scale, offset)
+        H.check(self._l.csdr_ingest_set_format(self.h, C.byref(f)))
+        self.format = f
+
+    def next_slot(self):
+        return self._l.csdr_ingest_next_slot(self.h)
+
+    def wait(self):
+        H.check(self._l.csdr_ingest_wait(self.h))
 
     def close(self):
         if self.h:

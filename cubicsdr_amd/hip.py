@@ -20,6 +20,8 @@ CSDR_DIGITAL_PSK, CSDR_DIGITAL_DPSK, CSDR_DIGITAL_ASK, CSDR_DIGITAL_QAM, CSDR_DI
 CSDR_DIGITAL_GMSK = 8
 DIGITAL_BY_NAME = {"PSK": 0, "DPSK": 1, "ASK": 2, "QAM": 3, "BPSK": 4, "QPSK": 5, "OOK": 6, "FSK": 7, "GMSK": 8}
 CSDR_DIGITAL_MAX_CARRY = 2048
+CSDR_IQ_CF32, CSDR_IQ_CS16, CSDR_IQ_CS8, CSDR_IQ_CU8, CSDR_IQ_CS12 = range(5)
+IQ_FORMAT_BY_NAME = {"CF32": 0, "CS16": 1, "CS8": 2, "CU8": 3, "CS12": 4}
 
 
 class DemodParams(C.Structure):
@@ -51,6 +53,10 @@ class GmskState(C.Structure):
 class DigitalState(C.Structure):
     _fields_ = [("r", C.c_float * 2), ("x_hat", C.c_float * 2), ("phi", C.c_float), ("n_carry", C.c_int32),
                 ("reserved", C.c_int32 * 2), ("carry", C.c_float * (2 * CSDR_DIGITAL_MAX_CARRY))]
+
+
+class IqFormat(C.Structure):
+    _fields_ = [("format", C.c_int32), ("offset", C.c_float), ("full_scale", C.c_double)]
 
 
 class P2pOp(C.Structure):
@@ -197,6 +203,13 @@ ABI = {
     "csdr_bank_fetch_digital_results": (_i, [_p, _i, C.POINTER(DigitalResult), _i, C.POINTER(_i)]),
     "csdr_bank_fetch_symbols": (_i, [_p, _i, _p, _i, C.POINTER(_i)]),
     "csdr_digital_run": (_i, [_p, C.POINTER(DigitalParams), _i64, _p, _i, C.POINTER(DigitalState), _p, _i, C.POINTER(_i), C.POINTER(_f)]),
+    "csdr_iq_format_bytes": (_i, [_i, _i64, C.POINTER(C.c_uint64)]),
+    "csdr_ingest_create_raw": (_i, [_p, _i64, _i, C.POINTER(IqFormat), _pp]),
+    "csdr_ingest_acquire_raw": (_i, [_p, _pp]),
+    "csdr_ingest_commit_raw": (_i, [_p, _i64, _i, _pp]),
+    "csdr_ingest_upload_raw": (_i, [_p, _p, _i64, _i, _pp]),
+    "csdr_ingest_set_format": (_i, [_p, C.POINTER(IqFormat)]),
+    "csdr_iq_convert": (_i, [_p, C.POINTER(IqFormat), _p, _i64, _i, _p]),
     "csdr_gmsk_run": (_i, [_p, C.POINTER(DigitalParams), _p, _i, C.POINTER(GmskState), _p, _p, _p, _i, C.POINTER(_i)]),
 }
 

@@ -8,6 +8,9 @@
 //                     block.  Reads land DIRECTLY in the block (no intermediate MTU buffer, no per-sample copy loop); the I/Q
 //                     exchange (:258-266) is not done here at all: the block carries a flag and the exchange happens while the block
 //                     crosses the link (csdr_ingest_upload).  numChannels / numElems: :668-693.
+//   RawStreamReblocker  the same for a stream opened in the radio's NATIVE format (CS16 / CS8 / CU8 / CS12 and the full scale getNativeStreamFormat
+//                     reports) instead of "CF32" (SoapySDRThread.cpp:88-90): the block holds the radio's bytes, crosses the link as they are
+//                     (csdr_ingest_upload_raw) and is widened to CF32 on the GPU -- the driver's per-sample conversion on a host core is gone.
 //   DeviceIngest      ONE transfer per block into a ring of HBM slots (csdr_ingest); the block then carries its device address, which
 //                     SDRPostThread and the spectrum processors read instead of uploading the host copy again (SDRPostThread.cpp:227-245
 //                     hands one buffer to all consumers).
@@ -42,6 +45,59 @@ struct IQStreamSource {
     virtual int readStream(float *buff, int maxElems) = 0;
 };
 
+// the same for a stream in the device's native format: up to `maxElems` samples of that format into `buff`
+struct RawIQStreamSource {
+    virtual ~RawIQStreamSource() = default;
+    virtual int readStream(void *buff, int maxElems) = 0;
+};
+
+// ---- native sample formats on the host (include/csdr_hip.h: the arithmetic the device kernel and this fall-back share bit for bit) ----------
+inline size_t iqSampleBytes(int format) { uint64_t b = 0; return csdr_iq_format_bytes(format, 1, &b) == CSDR_OK ? (size_t)b : 0; }
+// component k (0: I, 1: Q) of sample i as the integer the format stores
+inline int iqRawComponent(int format, const unsigned char *raw, size_t i, int k) {
+    switch (format) {
+    case CSDR_IQ_CS16: { int16_t v; std::memcpy(&v, raw + 4 * i + 2 * k, 2); return v; }
+    case CSDR_IQ_CS8: return (int8_t)raw[2 * i + k];
+    case CSDR_IQ_CU8: return raw[2 * i + k];
+    case CSDR_IQ_CS12: {
+        const unsigned v = (unsigned)raw[3 * i] | ((unsigned)raw[3 * i + 1] << 8) | ((unsigned)raw[3 * i + 2] << 16);
+        const int c = (int)((k ? v >> 12 : v) & 0xFFFu);
+        return c - ((c & 0x800) << 1);
+    }
+    default: return 0;
+    }
+}
+// y = ((float)x - offset) * s, s = (float)(1.0 / full_scale); the difference and the product are separate float32 operations
+inline void convertRawIQ(const csdr_iq_format &f, const unsigned char *raw, size_t n, bool swap, liquid_float_complex_t *out) {
+    if (f.format == CSDR_IQ_CF32) {
+        std::memcpy(out, raw, n * sizeof *out);
+        if (swap) for (size_t i = 0; i < n; ++i) std::swap(out[i].real, out[i].imag);
+        return;
+    }
+    const float s = (float)(1.0 / f.full_scale), offset = f.offset;
+    for (size_t i = 0; i < n; ++i) {
+        const float a = (float)iqRawComponent(f.format, raw, i, 0) - offset, b = (float)iqRawComponent(f.format, raw, i, 1) - offset;
+        const float ya = a * s, yb = b * s;
+        out[i].real = swap ? yb : ya; out[i].imag = swap ? ya : yb;
+    }
+}
+// I and Q of n raw samples change places, in the format's own units (the exchange is its own inverse and commutes with the conversion)
+inline void exchangeRawIQ(int format, unsigned char *raw, size_t n) {
+    switch (format) {
+    case CSDR_IQ_CF32: for (size_t i = 0; i < n; ++i) { unsigned char t[4]; std::memcpy(t, raw + 8 * i, 4); std::memcpy(raw + 8 * i, raw + 8 * i + 4, 4); std::memcpy(raw + 8 * i + 4, t, 4); } break;
+    case CSDR_IQ_CS16: for (size_t i = 0; i < n; ++i) { std::swap(raw[4 * i], raw[4 * i + 2]); std::swap(raw[4 * i + 1], raw[4 * i + 3]); } break;
+    case CSDR_IQ_CS8: case CSDR_IQ_CU8: for (size_t i = 0; i < n; ++i) std::swap(raw[2 * i], raw[2 * i + 1]); break;
+    case CSDR_IQ_CS12:
+        for (size_t i = 0; i < n; ++i) {
+            const unsigned v = (unsigned)raw[3 * i] | ((unsigned)raw[3 * i + 1] << 8) | ((unsigned)raw[3 * i + 2] << 16);
+            const unsigned w = (v >> 12) | ((v & 0xFFFu) << 12);
+            raw[3 * i] = (unsigned char)w; raw[3 * i + 1] = (unsigned char)(w >> 8); raw[3 * i + 2] = (unsigned char)(w >> 16);
+        }
+        break;
+    default: break;
+    }
+}
+
 // ---- block geometry of a sample rate (SoapySDRThread.cpp:668-693) -------------------------------------------------------------
 struct BlockGeometry {
     int channels = 1, elems = 0;
@@ -64,7 +120,12 @@ public:
     DeviceIngest(csdr_ctx *ctx, long long maxSamples, int depth = 4) : holds_((size_t)depth) {
         if (csdr_ingest_create(ctx, maxSamples, depth, &ing_) != CSDR_OK) throw std::runtime_error(std::string("csdr_ingest_create: ") + csdr_last_error());
     }
+    // a ring for blocks in the radio's native format (RawStreamReblocker): page-locked slots and link traffic of that size, CF32 in HBM
+    DeviceIngest(csdr_ctx *ctx, long long maxSamples, const csdr_iq_format &fmt, int depth = 4) : holds_((size_t)depth), raw_(true), fmt_(fmt) {
+        if (csdr_ingest_create_raw(ctx, maxSamples, depth, &fmt, &ing_) != CSDR_OK) throw std::runtime_error(std::string("csdr_ingest_create_raw: ") + csdr_last_error());
+    }
     ~DeviceIngest() { if (ing_) csdr_ingest_destroy(ing_); }
+    bool isRaw() const { return raw_; }
     // Moves blk.data over the link (exchanging I and Q on the way when blk.iqSwapPending) and records the HBM address in the block.
     // false: the slot that is next in the ring is still held by a consumer (or the transfer failed) -- the block stays host-only.
     // The transfer is a DMA from blk.data that may still be running on return: wait() before the buffer is rewritten or recycled.
@@ -72,9 +133,19 @@ public:
         const int k = csdr_ingest_next_slot(ing_);
         if (k < 0 || (holds_[(size_t)k] && holds_[(size_t)k].use_count() > 1)) return false;
         const float *dev = nullptr;
-        if (csdr_ingest_upload(ing_, reinterpret_cast<const float *>(blk.data.data()), (long long)blk.data.size(), blk.iqSwapPending ? 1 : 0, &dev) != CSDR_OK) return false;
+        size_t n = blk.data.size();
+        if (blk.rawSamples) {
+            // a native-format block: the radio's bytes cross the link, the GPU widens them (and exchanges I and Q when the block asks for it)
+            if (!raw_) return false;
+            if (std::memcmp(&fmt_, &blk.rawFormat, sizeof fmt_)) {                        // a changed full scale / offset / format applies from this block on
+                if (csdr_ingest_set_format(ing_, &blk.rawFormat) != CSDR_OK) return false;
+                fmt_ = blk.rawFormat;
+            }
+            n = blk.rawSamples;
+            if (csdr_ingest_upload_raw(ing_, blk.raw.data(), (long long)n, blk.iqSwapPending ? 1 : 0, &dev) != CSDR_OK) return false;
+        } else if (raw_ || csdr_ingest_upload(ing_, reinterpret_cast<const float *>(blk.data.data()), (long long)n, blk.iqSwapPending ? 1 : 0, &dev) != CSDR_OK) return false;
         holds_[(size_t)k] = std::make_shared<int>(k);
-        blk.deviceData = dev; blk.deviceSamples = blk.data.size(); blk.deviceHold = holds_[(size_t)k];
+        blk.deviceData = dev; blk.deviceSamples = n; blk.deviceHold = holds_[(size_t)k];
         return true;
     }
     void wait() { (void)csdr_ingest_wait(ing_); }
@@ -82,6 +153,8 @@ public:
 private:
     csdr_ingest *ing_ = nullptr;
     std::vector<std::shared_ptr<void>> holds_;
+    bool raw_ = false;
+    csdr_iq_format fmt_{};                        // raw ring: the format the ingest currently converts from
 };
 
 // ---- the device stream cut into blocks ----------------------------------------------------------------------------------------
@@ -187,6 +260,110 @@ private:
     std::atomic_bool swap_{false};
 };
 typedef StreamReblocker SDRBlockAssembler;          // (the name earlier revisions and INTEGRATION.md use)
+
+// ---- the device stream cut into blocks, in the radio's native format ------------------------------------------------------------
+// StreamReblocker's rules (SoapySDRThread.cpp:195-402) in raw units: every read lands straight behind what the block's `raw` bytes already hold,
+// the surplus of the last read opens the next block (3-byte samples included), a saturated consumer loses the block.  The block then goes to the
+// raw DeviceIngest as it is -- csdr_ingest_upload_raw widens it on the GPU and does the I/Q exchange on the way, `data` stays empty -- or, when
+// no ingest is bound or its next slot is still held, is widened here with the same arithmetic so that every consumer still finds CF32 `data`.
+class RawStreamReblocker {
+public:
+    explicit RawStreamReblocker(const csdr_iq_format &fmt, csdr_ctx *ctx = nullptr) : ctx_(ctx), fmt_(fmt), bps_(iqSampleBytes(fmt.format)), pool_("SDRThreadRawBuffers") {
+        if (!bps_) throw std::runtime_error("RawStreamReblocker: unknown sample format");
+    }
+    ~RawStreamReblocker() { for (void *p : pinned_) if (ctx_) (void)csdr_host_unregister(ctx_, p); }
+
+    void setSampleRate(long long rate) {
+        const BlockGeometry g = BlockGeometry::forRate(rate);
+        rate_.store(rate); channels_.store(g.channels); elems_.store(g.elems);
+    }
+    void setFrequency(long long f) { const long long lo = rate_.load() / 2; freq_.store(f < lo ? lo : f); }
+    void setMTU(int mtu) { mtu_.store(mtu); }
+    void setIQSwap(bool s) { swap_.store(s); }
+    // full scale / offset as the device reports them now (e.g. after a gain-mode change); same sample size; from the next block on
+    // false (and nothing changes): a full scale that is not finite and positive, a non-finite offset, an offset with a signed format
+    bool setScale(double fullScale, float offset) {
+        if (!std::isfinite(fullScale) || !(fullScale > 0.0) || !std::isfinite(offset) || (fmt_.format != CSDR_IQ_CU8 && offset != 0.0f)) return false;
+        std::lock_guard<std::mutex> g(fmtMu_);
+        fmt_.full_scale = fullScale; fmt_.offset = offset;
+        return true;
+    }
+    int getNumChannels() const { return channels_.load(); }
+    int getNumElems() const { return elems_.load(); }
+    int pendingOverflow() const { return (int)(spill_.size() / bps_); }              // samples
+    void bindIngest(DeviceIngest *ing) { ingest_ = ing; }
+
+    // Assemble and post ONE block; the return value follows StreamReblocker::readStream
+    int readStream(RawIQStreamSource &dev, const SDRThreadIQDataQueuePtr &out, const std::atomic_bool &stopping) {
+        const int want = elems_.load(), mtu = std::max(1, mtu_.load());
+        if (uploading_ && ingest_) ingest_->wait();                                   // (a pooled block may be the one whose upload is still reading it)
+        uploading_ = false;
+        SDRThreadIQDataPtr blk = pool_.getBuffer();
+        reserve(*blk, ((size_t)want + (size_t)mtu) * bps_);
+        unsigned char *base = blk->raw.data();
+        size_t have = std::min(spill_.size() / bps_, (size_t)want);                   // samples
+        bool swapped = false;
+        if (have) {
+            std::memcpy(base, spill_.data(), have * bps_);
+            spill_.erase(spill_.begin(), spill_.begin() + (long)(have * bps_));
+            swapped = spillSwapped_;
+        }
+        int code = 0;
+        while ((int)have < want && !stopping.load()) {
+            const bool sw = swap_.load();
+            code = dev.readStream(base + have * bps_, mtu);                            // straight into the block
+            if (code <= 0) break;
+            if (have == 0) swapped = sw;
+            else if (sw != swapped) { exchangeRawIQ(fmt_.format, base, have); swapped = sw; }   // the option changed inside this block
+            have += (size_t)code;
+        }
+        if ((int)have > want) {                                                        // the last read ran past the block: carry the rest, in raw units
+            spill_.insert(spill_.end(), base + (size_t)want * bps_, base + have * bps_);
+            spillSwapped_ = swapped;
+            have = (size_t)want;
+        }
+        if (have == 0 || stopping.load() || out->full()) return 0;
+        blk->rawSamples = have;
+        { std::lock_guard<std::mutex> g(fmtMu_); blk->rawFormat = fmt_; }
+        blk->frequency = freq_.load(); blk->sampleRate = rate_.load(); blk->numChannels = channels_.load(); blk->dcCorrected = false;
+        blk->iqSwapPending = swapped;
+        blk->dropDeviceCopy();
+        blk->data.clear();
+        const bool inHbm = ingest_ && ingest_->upload(*blk);
+        uploading_ = inHbm;
+        if (!inHbm) {                                                                  // host fall-back: the header's arithmetic, exchange included
+            blk->data.resize(have);
+            convertRawIQ(blk->rawFormat, base, have, swapped, blk->data.data());
+        }
+        blk->iqSwapPending = false;
+        if (!out->try_push(blk)) return 0;
+        return code;
+    }
+
+private:
+    // capacity only: the pooled vector keeps its storage, page-locked once per storage so that the transfer is a DMA from the block
+    void reserve(SDRThreadIQData &blk, size_t bytes) {
+        if (blk.raw.size() >= bytes) return;
+        const void *before = blk.raw.empty() ? nullptr : blk.raw.data();
+        blk.raw.resize(bytes);
+        if (!ctx_ || blk.raw.data() == before) return;
+        auto it = std::find(pinned_.begin(), pinned_.end(), (void *)before);
+        if (it != pinned_.end()) { (void)csdr_host_unregister(ctx_, *it); pinned_.erase(it); }
+        if (csdr_host_register(ctx_, blk.raw.data(), blk.raw.size()) == CSDR_OK) pinned_.push_back(blk.raw.data());
+    }
+    csdr_ctx *ctx_;
+    csdr_iq_format fmt_;
+    std::mutex fmtMu_;
+    size_t bps_;
+    DeviceIngest *ingest_ = nullptr;
+    ReBuffer<SDRThreadIQData> pool_;
+    std::vector<unsigned char> spill_;
+    bool spillSwapped_ = false, uploading_ = false;
+    std::vector<void *> pinned_;
+    std::atomic<long long> rate_{0}, freq_{0};
+    std::atomic_int channels_{1}, elems_{0}, mtu_{0};
+    std::atomic_bool swap_{false};
+};
 
 // ---- audio egress -------------------------------------------------------------------------------------------------------------
 // One source per demodulator (the reference binds one AudioThread per DemodulatorInstance to the device's controller thread,

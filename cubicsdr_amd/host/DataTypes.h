@@ -6,6 +6,7 @@
 #include <memory>
 #include <vector>
 
+#include "../../include/csdr_hip.h"
 #include "ThreadBlockingQueue.h"
 
 struct liquid_float_complex_t { float real, imag; };     // layout of liquid_float_complex (liquid.h:149-157)
@@ -30,6 +31,13 @@ public:
     int numChannels = 0;
     bool iqSwapPending = false;               // internal to the block assembler: `data` still holds Q, I (exchanged during the transfer)
     std::vector<liquid_float_complex_t> data;
+    // A block read in the radio's own sample format (RawStreamReblocker): `raw` holds rawSamples samples of rawFormat.  Such a block carries
+    // EITHER a device copy (the ingest widened it on the GPU; `data` stays empty) OR host CF32 in `data` (converted on the host).
+    // SDRPostThread reads it through numSamples() / deviceData; what it hands on to the visual queues always carries host samples again.
+    std::vector<unsigned char> raw;
+    size_t rawSamples = 0;
+    csdr_iq_format rawFormat{};
+    size_t numSamples() const { return data.empty() ? deviceSamples : data.size(); }     // the block's length, wherever its CF32 samples live
     virtual ~SDRThreadIQData() = default;
 };
 typedef std::shared_ptr<SDRThreadIQData> SDRThreadIQDataPtr;
@@ -41,6 +49,7 @@ public:
     long long frequency = 0;
     long long sampleRate = 0;
     std::vector<liquid_float_complex_t> data;
+    size_t numSamples() const { return data.empty() ? deviceSamples : data.size(); }     // (a block that lives in HBM only has no host samples)
     virtual ~DemodulatorThreadIQData() = default;
 };
 typedef std::shared_ptr<DemodulatorThreadIQData> DemodulatorThreadIQDataPtr;

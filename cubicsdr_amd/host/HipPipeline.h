@@ -228,7 +228,7 @@ public:
         while (!stopping) {
             SDRThreadIQDataPtr in;
             if (!iqIn->pop(in, HEARTBEAT_CHECK_PERIOD_MICROS)) continue;      // SDRPostThread.cpp:170
-            if (!in || in->data.empty()) continue;
+            if (!in || in->numSamples() == 0) continue;
             processBlock(*in, iqOut, iqVisual);
             ++blocksProcessed;
         }
@@ -256,8 +256,9 @@ private:
     void processBlock(SDRThreadIQData &in, const DemodulatorThreadInputQueuePtr &iqOut, const DemodulatorThreadInputQueuePtr &iqVisual) {
         const int M = in.numChannels > 1 ? in.numChannels : 1;
         // whole frames only (the reference's channelizer loop steps by numChannels, :449; SoapySDRThread hands out multiples, :668-674)
-        const int n = ((int)in.data.size() / M) * M;
+        const int n = ((int)in.numSamples() / M) * M;                               // (a native-format block may live in HBM only: `data` is empty)
         if (n <= 0) return;
+        const bool inHbm = in.deviceData && in.deviceSamples >= (size_t)n;          // already in HBM (DeviceIngest): no second transfer
         const int mode = chanMode.load();
         if (in.sampleRate != sampleRate_ || M != numChannels_ || n > maxBlock_ || mode != lastChanMode_) {      // initPFBCH :401-414, initPFBCH2 :458-470
             // room for blocks up to twice the nominal 1/60 s (a longer one re-initialises, which also rebuilds every demodulator:
@@ -272,7 +273,7 @@ private:
         if (M == 1) {
             // runSingleCH (:248-299): the DC blocker runs on EVERY block; the DC-corrected data is what the main spectrum, the
             // waterfall and (when a demodulator is active) the demodulator spectrum see
-            CSDR_STAGE_TRY(csdr_post_execute(post_, (const float *)in.data.data(), 0, 1, n, in.frequency), "csdr_post_execute");
+            CSDR_STAGE_TRY(csdr_post_execute(post_, inHbm ? in.deviceData : (const float *)in.data.data(), inHbm ? 1 : 0, 1, n, in.frequency), "csdr_post_execute");
             // the corrected block comes back to the host only for a consumer that is bound (a D2H copy + stream wait per block
             // otherwise bought nothing and kept the demodulators waiting behind it); the demodulators read it on the device
             auto iqActiveQ = std::static_pointer_cast<DemodulatorThreadInputQueue>(getOutputQueue("IQActiveDemodVisualDataOutput"));
@@ -291,6 +292,13 @@ private:
             DemodulatorThreadIQDataPtr vis = visualBuffers_.getBuffer();
             vis->frequency = in.frequency; vis->sampleRate = in.sampleRate; vis->data = in.data;
             vis->shareDeviceCopy(in);                                               // the spectrum reads the block where the ingest put it
+            if (vis->data.empty() && in.deviceData && in.deviceSamples) {
+                // a native-format block lives in HBM only, and this queue also feeds consumers that work on the host (the waterfall's
+                // FFTDataDistributor buffers and cuts the samples themselves): they get the widened block back -- only here, where such a
+                // consumer is bound, like the single-channel branch's read-back above
+                vis->data.resize(in.deviceSamples);
+                CSDR_STAGE_TRY(csdr_dev_download(ctx_, vis->data.data(), in.deviceData, (uint64_t)in.deviceSamples * sizeof(liquid_float_complex_t)), "csdr_dev_download");
+            }
             iqOut->try_push(vis);
             if (iqVisual) iqVisual->try_push(vis);
         }
@@ -336,7 +344,7 @@ private:
         auto iqActive = std::static_pointer_cast<DemodulatorThreadInputQueue>(getOutputQueue("IQActiveDemodVisualDataOutput"));
         if (M == 1) {
             if (iqActive && singleOut_) iqActive->try_push(singleOut_);              // :289-292
-        } else if (in.deviceData && in.deviceSamples >= (size_t)n)                  // already in HBM (DeviceIngest): no second transfer
+        } else if (inHbm)
             CSDR_STAGE_TRY(csdr_post_execute(post_, in.deviceData, 1, 1, n, in.frequency), "csdr_post_execute");
         else CSDR_STAGE_TRY(csdr_post_execute(post_, (const float *)in.data.data(), 0, 1, n, in.frequency), "csdr_post_execute");
         CSDR_STAGE_TRY(csdr_bank_execute(bank_, post_), "csdr_bank_execute");
@@ -588,15 +596,16 @@ protected:
         DemodulatorThreadIQDataPtr iq;
         if (!input->pop(iq, HEARTBEAT_CHECK_PERIOD_MICROS) || !iq) return;
         std::lock_guard<std::mutex> g(busy_run);
-        if (!fftSize || iq->data.empty()) return;
+        const size_t n = iq->numSamples();
+        if (!fftSize || !n) return;
         const size_t N = 2 * (size_t)fftSize;
         CSDR_STAGE_TRY(csdr_spec_set_input_frequency(spec_, iq->frequency), "csdr_spec_set_input_frequency");
         CSDR_STAGE_TRY(csdr_spec_set_input_rate(spec_, iq->sampleRate), "csdr_spec_set_input_rate");
         // inputs of at least 2*fftSize samples are transformed directly (:401-404); shorter ones go through the
         // fftLastData priming / overlap rule (:406-420)
-        const int mode = iq->data.size() >= N ? CSDR_SPEC_FIRST_FRAME : CSDR_SPEC_LINES;
-        const bool inHbm = iq->deviceData && iq->deviceSamples == iq->data.size();     // the ingest's copy: read it in place
-        CSDR_STAGE_TRY(csdr_spec_process(spec_, inHbm ? iq->deviceData : (const float *)iq->data.data(), inHbm ? 1 : 0, 1, (int)iq->data.size(), mode), "csdr_spec_process");
+        const int mode = n >= N ? CSDR_SPEC_FIRST_FRAME : CSDR_SPEC_LINES;
+        const bool inHbm = iq->deviceData && iq->deviceSamples == n;                   // the ingest's copy: read it in place
+        CSDR_STAGE_TRY(csdr_spec_process(spec_, inHbm ? iq->deviceData : (const float *)iq->data.data(), inHbm ? 1 : 0, 1, (int)n, mode), "csdr_spec_process");
         if (csdr_spec_frames(spec_) < 1) return;                                     // the input only primed fftLastData
         SpectrumVisualDataPtr out = outputBuffers.getBuffer();
         out->spectrum_points.resize(fftSize * 2);

@@ -10,6 +10,7 @@
  * its demodulators (csdr_post + csdr_bank: a call that takes two handles uses both) beside the spectrum thread (csdr_spec).
  *
  * Sample format everywhere: interleaved complex float32 {re, im} (liquid_float_complex, liquid.h:149-157).
+ * (A radio's native integer formats enter through the raw ingest, which widens them to that on the GPU: see "ingest of a radio's native sample format".)
  * "dev" pointers are HIP device pointers resident in HBM; "host" pointers are ordinary host memory.
  *
  * Batching: the reference handles one SDRThreadIQData block per loop turn (60 blocks/s,
@@ -442,6 +443,59 @@ int  csdr_ingest_commit(csdr_ingest *ing, int64_t n_samples, int iq_swap, const 
 int  csdr_ingest_upload(csdr_ingest *ing, const float *host_iq, int64_t n_samples, int iq_swap, const float **dev_iq);
 int  csdr_ingest_next_slot(const csdr_ingest *ing);
 int  csdr_ingest_wait(csdr_ingest *ing);             /* blocks until the last transfer has left its source buffer: call before rewriting or recycling the block just uploaded */
+
+/* ------------------------------------------------------------------ ingest of a radio's native sample format
+ * Receivers deliver 8-, 12- or 16-bit integers (SoapySDR's "CU8", "CS8", "CS12", "CS16", with the full scale getNativeStreamFormat reports); the
+ * reference asks the driver for "CF32" (SoapySDRThread.cpp:88-90), so the widening runs sample by sample on a host core before readStream
+ * (:253, :294-308) sees the data.  A raw ingest carries the radio's own bytes over the link -- 4, 3 or 2 per sample instead of 8 -- in page-locked
+ * slots of that size, and widens them on the GPU into the same CF32 ring in HBM that every consumer reads.
+ *
+ * A sample is a pair (I, Q), little-endian:
+ *   CSDR_IQ_CF32  8 bytes  float I, float Q       (accepted so that callers have one code path: no conversion runs, full_scale / offset are unused)
+ *   CSDR_IQ_CS16  4 bytes  int16 I, int16 Q
+ *   CSDR_IQ_CS8   2 bytes  int8 I, int8 Q
+ *   CSDR_IQ_CU8   2 bytes  uint8 I, uint8 Q       (offset binary)
+ *   CSDR_IQ_CS12  3 bytes  b0 = I[7:0], b1 = Q[3:0] << 4 | I[11:8], b2 = Q[11:4]; both sign-extended from 12 bits
+ * THE ARITHMETIC, which the device kernel, the host mirror's fall-back and the tests' restatement share bit for bit: every component is
+ *     y = ((float)x - offset) * s,    s = (float)(1.0 / full_scale)
+ * with s rounded once on the host, the subtraction and the product each rounded once in float32 and never contracted into one operation
+ * ((float)x is exact for all these widths).  With iq_swap the two CONVERTED components change places.  This is the library's own definition:
+ * it is not claimed to equal any particular driver's host conversion.
+ * Refused with CSDR_EINVAL: an unknown format, a full_scale that is not finite and positive, a non-finite offset, a non-zero offset with a
+ * signed format (offset is the caller's choice for CU8: 128, 127.5, or the 127.4 some RTL-SDR drivers use). */
+#define CSDR_IQ_CF32 0
+#define CSDR_IQ_CS16 1
+#define CSDR_IQ_CS8  2
+#define CSDR_IQ_CU8  3
+#define CSDR_IQ_CS12 4
+typedef struct csdr_iq_format {
+    int32_t format;            /* CSDR_IQ_* */
+    float   offset;            /* subtracted from (float)x: 0 for the signed formats */
+    double  full_scale;        /* 32768, 2048, 128 ...: y = 1 at x - offset = full_scale */
+} csdr_iq_format;
+CSDR_STATIC_ASSERT(sizeof(csdr_iq_format) == 16 && offsetof(csdr_iq_format, full_scale) == 8, "csdr_iq_format layout");
+/* bytes n_samples samples occupy in `format` */
+int  csdr_iq_format_bytes(int format, int64_t n_samples, uint64_t *bytes);
+/* A ring like csdr_ingest_create's whose page-locked slots hold max_samples samples of *fmt (csdr_iq_format_bytes, not 8 * max_samples); the HBM
+ * ring, the events and the lifetime of the returned device pointer (valid until depth - 1 further commits) are the same.  acquire_raw gives the slot
+ * the reader fills with the radio's bytes; commit_raw moves its first n_samples over the link as they are -- ONE DMA into a staging buffer in HBM that
+ * the ingest owns -- and converts them into the HBM slot behind it, both on the ingest's transfer stream.  (The converting kernel reading the mapped
+ * slot over the link, as the exchanging commit of the typed ring does, was measured too: slower beside a running pipeline) */
+int  csdr_ingest_create_raw(csdr_ctx *ctx, int64_t max_samples, int depth, const csdr_iq_format *fmt, csdr_ingest **out);
+int  csdr_ingest_acquire_raw(csdr_ingest *ing, void **host_slot);
+int  csdr_ingest_commit_raw(csdr_ingest *ing, int64_t n_samples, int iq_swap, const float **dev_iq);
+/* the same for a block in the caller's own memory (page-locked with csdr_host_register or pageable, any alignment): ONE hipMemcpyAsync of the raw
+ * bytes into the same staging buffer (allocated on first use), then the conversion in HBM, both on the transfer stream.  The previous upload is
+ * waited for first, as in csdr_ingest_upload. */
+int  csdr_ingest_upload_raw(csdr_ingest *ing, const void *host_raw, int64_t n_samples, int iq_swap, const float **dev_iq);
+/* change full_scale / offset, or switch to a format whose samples are no larger than those the ring was created for, between blocks: takes effect at
+ * the next commit / upload (what is already enqueued keeps the format it was enqueued with) */
+int  csdr_ingest_set_format(csdr_ingest *ing, const csdr_iq_format *fmt);
+/* the conversion kernel alone, for parity checks: n_samples of *fmt at raw_host -> out_host[2 * n_samples] floats */
+int  csdr_iq_convert(csdr_ctx *ctx, const csdr_iq_format *fmt, const void *raw_host, int64_t n_samples, int iq_swap, float *out_host);
+/* The typed calls (csdr_ingest_acquire / _commit / _upload) on a raw ingest and the raw calls on a typed one return CSDR_ESTATE (a raw ingest whose
+ * format is CSDR_IQ_CF32 is still a raw ingest: its slots are reached through the raw calls); n_samples beyond the slot is CSDR_ERANGE.  Every
+ * refusal enqueues nothing and leaves the ring where it was. */
 
 /* ------------------------------------------------------------------ one stream over several GPUs
  * Replaces the fan-out point SDRPostThread.cpp:389-396 (one block pushed to every demodulator's queue) when the DemodulatorInstances
