@@ -105,7 +105,7 @@ extern "C" void csdr_bank_destroy(csdr_bank *b) {
         if (b->stage_ev[r]) (void)hipEventDestroy(b->stage_ev[r]);
     }
     b->bout_h.release();
-    b->pcm.release(); b->pcm_jobs.release(); b->dig_jobs.release();
+    b->pcm.release(); b->pcm_jobs.release(); b->dig_jobs.release(); b->tab_jobs.release();
     delete b;
 }
 

@@ -1,5 +1,6 @@
 // csdr_digital.hip -- the digital lab (reference src/modules/modem/digital/): configuration of digital slots, their per-batch plan and launch behind
-// the bank's front-end, the result fetches, csdr_digital_run (the decision kernel alone) and csdr_gmsk_run (the GMSK kernels alone).  Kernels:
+// the bank's front-end, the result fetches, csdr_digital_run (the decision kernel alone), csdr_gmsk_run (the GMSK kernels alone), the table-driven slots
+// (csdr_bank_configure_table_slot, csdr_design_rings, csdr_table_run).  Kernels:
 // kernels_digital.hpp; DESIGN 15.
 #include <algorithm>
 #include <cmath>
@@ -25,7 +26,7 @@ struct DigSlot {
     int carry = 0, stash_cur = 0;            // FSK: samples held (kit->inputBuffer), which stash copy holds them
     int st_cur[kDigRecords] = {0};           // which copy of each constellation's state is current
     void *mem = nullptr;                     // device: sym [cap_sym] | bevm [max_blocks] | st [8][2][8] | stash [2][kDigFskMaxK] | map [M]; GMSK: sym [cap_sym] |
-                                             // taps | history | plan | phase differences, nothing of the others
+                                             // taps | history | plan | phase differences, nothing of the others; table slot: sym | bevm | st | tables
     uint32_t *sym = nullptr;
     float *bevm = nullptr, *st = nullptr;
     float2 *stash = nullptr;
@@ -47,6 +48,10 @@ struct DigSlot {
     float *gphi = nullptr;                   // device: the batch's phase-difference stream [cap_phi]
     int64_t cap_phi = 0;
     std::vector<GmskBlock> gblk;             // the batch's plan [NB + 1]
+    // table slot (CSDR_DIGITAL_TABLE): the reference's per-"cons" objects; idx picks one, its state is record idx of st
+    std::vector<int> tab_cons;               // n_points of each table
+    std::vector<float> tab_sens;
+    TableDev *tab_d = nullptr;               // device (inside mem): [tab_cons.size()]
     ~DigSlot() { if (mem) (void)hipFree(mem); }
 };
 
@@ -245,10 +250,124 @@ extern "C" int csdr_bank_configure_digital_slot(csdr_bank *b, int slot, const cs
     return CSDR_OK;
 }
 
+// a caller's constellation as the kernel reads it, or the refusal
+static int table_device(const csdr_constellation &c, TableDev *t, float *sens) {
+    memset(t, 0, sizeof *t);
+    if (c.rule != CSDR_TABLE_NEAREST && c.rule != CSDR_TABLE_RINGS && c.rule != CSDR_TABLE_QUADRANT) return fail(CSDR_EINVAL, "constellation rule %d", c.rule);
+    if (!pow2_in(c.n_points, 2, CSDR_TABLE_MAX_POINTS)) return fail(CSDR_EINVAL, "constellation of %d points: a power of two in 2 .. 256", c.n_points);
+    if (!(c.sensitivity >= 0.0f) || !std::isfinite(c.sensitivity)) return fail(CSDR_EINVAL, "constellation sensitivity %g", (double)c.sensitivity);
+    *sens = c.sensitivity == 0.0f ? 0.005f : c.sensitivity;
+    t->rule = c.rule; t->n_points = c.n_points;
+    for (int i = 0; i < c.n_points; ++i) {
+        if (!std::isfinite(c.points[2 * i]) || !std::isfinite(c.points[2 * i + 1])) return fail(CSDR_EINVAL, "constellation point %d is not finite", i);
+        t->points[i] = make_float2(c.points[2 * i], c.points[2 * i + 1]);
+    }
+    if (c.rule == CSDR_TABLE_NEAREST) return CSDR_OK;
+    if (c.rule == CSDR_TABLE_QUADRANT) {       // the fold's premise: quadrant q of the table is the first quadrant's points under q's sign changes
+        const int m = c.n_points / 4;
+        if (m < 1) return fail(CSDR_EINVAL, "a folded constellation needs at least 4 points");
+        for (int i = 0; i < m; ++i) {
+            const float2 a = t->points[i];
+            const float2 w[3] = {make_float2(a.x, -a.y), make_float2(-a.x, a.y), make_float2(-a.x, -a.y)};
+            for (int q = 1; q < 4; ++q) {
+                const float2 p = t->points[i + q * m];
+                if (p.x != w[q - 1].x || p.y != w[q - 1].y) return fail(CSDR_EINVAL, "point %d is not point %d folded into quadrant %d", i + q * m, i, q);
+            }
+        }
+        return CSDR_OK;
+    }
+    if (c.n_rings < 1 || c.n_rings > CSDR_TABLE_MAX_RINGS) return fail(CSDR_EINVAL, "constellation of %d rings: 1 .. 8", c.n_rings);
+    t->n_rings = c.n_rings;
+    int base = 0;
+    for (int l = 0; l < c.n_rings; ++l) {
+        const int p = c.ring_size[l];
+        if (p < 1 || p > c.n_points - base) return fail(CSDR_EINVAL, "ring %d of %d points: the rings must hold the %d points between them", l, p, c.n_points);
+        if (!std::isfinite(c.ring_phase[l])) return fail(CSDR_EINVAL, "ring %d: phase is not finite", l);
+        if (l + 1 < c.n_rings && !(c.ring_slicer[l] > (l ? c.ring_slicer[l - 1] : 0.0f) && std::isfinite(c.ring_slicer[l])))
+            return fail(CSDR_EINVAL, "ring slicer %d = %g does not ascend", l, (double)c.ring_slicer[l]);
+        t->ring_size[l] = p; t->ring_base[l] = base;
+        t->ring_phase[l] = c.ring_phase[l];
+        t->ring_slicer[l] = l + 1 < c.n_rings ? c.ring_slicer[l] : 0.0f;
+        t->ring_dphi[l] = (float)(2.0 * M_PI / (double)p);
+        base += p;
+    }
+    if (base != c.n_points) return fail(CSDR_EINVAL, "the rings hold %d points of %d", base, c.n_points);
+    bool seen[CSDR_TABLE_MAX_POINTS] = {false};
+    for (int s = 0; s < c.n_points; ++s) {
+        const int k = c.ring_map[s];
+        if (k >= c.n_points || seen[k]) return fail(CSDR_EINVAL, "ring_map is not a permutation (symbol %d -> %d)", s, k);
+        seen[k] = true;
+        t->inv[k] = (uint8_t)s;
+    }
+    return CSDR_OK;
+}
+
+extern "C" int csdr_design_rings(const float *points, int n_points, csdr_constellation *out) {
+    if (!points || !out) return fail(CSDR_EINVAL, "null argument");
+    design::RingPlan r;
+    if (!design::design_rings(points, n_points, &r))
+        return fail(CSDR_EINVAL, "csdr_design_rings: %d points are not 2^k (2 .. 256) distinct points on at most 8 concentric, evenly spaced rings", n_points);
+    memset(out, 0, sizeof *out);
+    out->rule = CSDR_TABLE_RINGS; out->n_points = n_points; out->n_rings = r.n_rings;
+    memcpy(out->points, points, (size_t)2 * n_points * sizeof(float));
+    for (int l = 0; l < r.n_rings; ++l) {
+        out->ring_size[l] = r.size[l]; out->ring_radius[l] = r.radius[l]; out->ring_phase[l] = r.phase[l]; out->ring_slicer[l] = r.slicer[l];
+    }
+    memcpy(out->ring_map, r.map, (size_t)n_points);
+    return CSDR_OK;
+}
+
+extern "C" int csdr_bank_configure_table_slot(csdr_bank *b, int slot, const csdr_demod_params *p, const csdr_constellation *tables, int n_tables,
+                                              const csdr_post *post) {
+    DeviceScope dev__(b ? b->ctx : nullptr);
+    if (!b || !p || !tables || !post) return fail(CSDR_EINVAL, "null argument");
+    if (p->modem != CSDR_MODEM_DIGITAL) return fail(CSDR_EINVAL, "csdr_bank_configure_table_slot: modem must be CSDR_MODEM_DIGITAL");
+    if (slot < 0 || slot >= b->max_demods) return fail(CSDR_EINVAL, "slot out of range");
+    if (p->bandwidth <= 0) return fail(CSDR_EINVAL, "bad rates");
+    static_assert(CSDR_TABLE_MAX_TABLES <= kDigRecords, "one state record per table");
+    if (n_tables < 1 || n_tables > CSDR_TABLE_MAX_TABLES) return fail(CSDR_EINVAL, "%d tables: 1 .. %d", n_tables, CSDR_TABLE_MAX_TABLES);
+    auto d = std::make_shared<DigSlot>();
+    std::vector<TableDev> th((size_t)n_tables);
+    d->tab_cons.resize((size_t)n_tables); d->tab_sens.resize((size_t)n_tables);
+    for (int i = 0; i < n_tables; ++i) {       // every check first: a refusal leaves the slot as it was
+        if (int rc = table_device(tables[i], &th[i], &d->tab_sens[i])) return rc;
+        d->tab_cons[i] = tables[i].n_points;
+        for (int q = 0; q < i; ++q)
+            if (d->tab_cons[q] == d->tab_cons[i]) return fail(CSDR_EINVAL, "tables %d and %d both hold %d points: \"cons\" could not tell them apart", q, i, d->tab_cons[i]);
+    }
+    d->p = csdr_digital_params{};
+    d->p.kind = CSDR_DIGITAL_TABLE; d->p.cons = d->tab_cons[0];
+    d->g.scheme = DIG_TABLE; d->idx = 0; d->sens = d->tab_sens[0];
+    csdr_demod_params q = *p;
+    q.bandwidth = p->bandwidth < 500 ? 500 : p->bandwidth;               // ModemDigital.cpp:21-26
+    if (int rc = bank_configure_slot(b, slot, &q, post)) return rc;      // (resets the slot, its digital stage included)
+    SlotHost &s = b->slots[slot];
+    d->cap_sym = s.cfg.cap_iq;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_sym = carve((size_t)d->cap_sym * sizeof(uint32_t)), o_bevm = carve((size_t)b->max_blocks * sizeof(float));
+    const size_t o_st = carve((size_t)kDigRecords * 2 * kDigStateFloats * sizeof(float)), o_tab = carve((size_t)n_tables * sizeof(TableDev));
+    if (hipMalloc(&d->mem, off) != hipSuccess) { d->mem = nullptr; s.configured = false; return fail(CSDR_ENOMEM, "table slot of %zu bytes", off); }
+    char *base = (char *)d->mem;
+    d->sym = (uint32_t *)(base + o_sym); d->bevm = (float *)(base + o_bevm); d->st = (float *)(base + o_st); d->tab_d = (TableDev *)(base + o_tab);
+    // modemcf_create: r = x_hat = 0 (EVM 0) in every object.  A failure leaves the slot unconfigured.
+    if (hipMemset(d->mem, 0, off) != hipSuccess || hipMemcpy(d->tab_d, th.data(), th.size() * sizeof(TableDev), hipMemcpyHostToDevice) != hipSuccess) {
+        s.configured = false;
+        return fail(CSDR_EHIP, "table slot initialisation: %s", hipGetErrorString(hipGetLastError()));
+    }
+    s.dig = d;
+    return CSDR_OK;
+}
+
 extern "C" int csdr_bank_set_digital_cons(csdr_bank *b, int slot, int cons) {
     if (!b || slot < 0 || slot >= b->max_demods || !b->slots[slot].configured || !b->slots[slot].dig) return fail(CSDR_EINVAL, "not a digital slot");
     DigSlot &d = *b->slots[slot].dig;
     const int kind = d.p.kind;
+    if (kind == CSDR_DIGITAL_TABLE) {          // a pointer move among the objects created up front
+        for (size_t i = 0; i < d.tab_cons.size(); ++i)
+            if (d.tab_cons[i] == cons) { d.idx = (int)i; d.p.cons = cons; d.sens = d.tab_sens[i]; return CSDR_OK; }
+        return fail(CSDR_EUNSUPPORTED, "cons %d: the slot holds no table of that size", cons);
+    }
     if (kind != CSDR_DIGITAL_PSK && kind != CSDR_DIGITAL_DPSK && kind != CSDR_DIGITAL_ASK && kind != CSDR_DIGITAL_QAM)
         return fail(CSDR_EINVAL, "this modem has no \"cons\" setting");
     csdr_digital_params np = d.p;
@@ -351,12 +470,45 @@ static int gmsk_launch(csdr_bank *b, const std::vector<int> &slots) {
     return CSDR_OK;
 }
 
+// the table slots of the batch: one table_demod launch, on the audio lane behind the front-end
+static int table_launch(csdr_bank *b, const std::vector<int> &slots, const BlockPlan *plans_d, int NB) {
+    if (slots.empty()) return CSDR_OK;
+    csdr_ctx *c = b->ctx;
+    const int nj = (int)slots.size();
+    if (int rc = b->tab_jobs.reserve((size_t)b->max_demods)) return rc;
+    std::vector<TableJob> &jh = b->tab_jobs_h;
+    jh.assign((size_t)nj, TableJob{});
+    int gx = 1;
+    for (int i = 0; i < nj; ++i) {
+        const int si = slots[i];
+        SlotHost &s = b->slots[si];
+        DigSlot &d = *s.dig;
+        TableJob &j = jh[i];
+        j.iq = s.cfg.iq + (size_t)s.last_parity * ((size_t)kIqHist + s.cfg.cap_iq) + kIqHist;     // the batch's resampled IQ (csdr_bank_fetch_iq)
+        j.n = std::min(d.n, d.cap_sym); j.nb = NB; j.plan = plans_d + (size_t)si * (NB + 1);
+        j.sym = d.sym; j.bevm = d.bevm; j.tab = d.tab_d + d.idx;
+        j.st_rd = d.st + (size_t)(2 * d.idx + d.st_cur[d.idx]) * kDigStateFloats;
+        j.st_wr = d.st + (size_t)(2 * d.idx + (d.st_cur[d.idx] ^ 1)) * kDigStateFloats;
+        gx = std::max(gx, (j.n + kTabThreads - 1) / kTabThreads);
+        if (d.n > 0) d.st_cur[d.idx] ^= 1;
+        d.nsym = d.nsym_plan; d.ran = true;
+    }
+    CSDR_HIP_TRY(hipMemcpyAsync(b->tab_jobs.p, jh.data(), (size_t)nj * sizeof(TableJob), hipMemcpyHostToDevice, c->lanes[LANE_AUDIO]));
+    CSDR_LAUNCH(c, LANE_AUDIO, KID_DIGITAL, table_demod, dim3(gx, nj), dim3(kTabThreads), sizeof(TableDev), (const TableJob *)b->tab_jobs.p);
+    CSDR_HIP_TRY(hipGetLastError());
+    return CSDR_OK;
+}
+
 int bank_digital_launch(csdr_bank *b, const BlockPlan *plans_d, int NB) {
     if (b->dig_run.empty()) return CSDR_OK;
     csdr_ctx *c = b->ctx;
-    std::vector<int> run, gmsk;
-    for (int si : b->dig_run) (b->slots[si].dig->p.kind == CSDR_DIGITAL_GMSK ? gmsk : run).push_back(si);
+    std::vector<int> run, gmsk, table;
+    for (int si : b->dig_run) {
+        const int kind = b->slots[si].dig->p.kind;
+        (kind == CSDR_DIGITAL_GMSK ? gmsk : kind == CSDR_DIGITAL_TABLE ? table : run).push_back(si);
+    }
     if (int rc = gmsk_launch(b, gmsk)) return rc;
+    if (int rc = table_launch(b, table, plans_d, NB)) return rc;
     if (run.empty()) return CSDR_OK;
     const int nj = (int)run.size();
     if (int rc = b->dig_jobs.reserve((size_t)b->max_demods * sizeof(DigJob))) return rc;
@@ -492,6 +644,52 @@ extern "C" int csdr_digital_run(csdr_ctx *c, const csdr_digital_params *dp, int6
         state->r[0] = w[0]; state->r[1] = w[1]; state->x_hat[0] = w[2]; state->x_hat[1] = w[3]; state->phi = w[4];
     }
     *n_symbols = nsym;
+    if (evm_last) *evm_last = evm;
+    return CSDR_OK;
+}
+
+extern "C" int csdr_table_run(csdr_ctx *c, const csdr_constellation *table, const float *iq_host, int n, csdr_digital_state *state,
+                              uint32_t *sym_host, int cap_symbols, int *n_symbols, float *evm_last) {
+    DeviceScope dev__(c);
+    if (!c || !table || !state || !n_symbols || n < 0 || (n > 0 && !iq_host)) return fail(CSDR_EINVAL, "bad argument");
+    TableDev th;
+    float sens;
+    if (int rc = table_device(*table, &th, &sens)) return rc;
+    if (n > cap_symbols || (n > 0 && !sym_host)) return fail(CSDR_ERANGE, "need room for %d symbols", n);
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_job = carve(sizeof(TableJob)), o_plan = carve(2 * sizeof(BlockPlan)), o_bevm = carve(sizeof(float)),
+                 o_st = carve(2 * kDigStateFloats * sizeof(float)), o_iq = carve((size_t)std::max(1, n) * sizeof(float2)),
+                 o_sym = carve((size_t)std::max(1, n) * sizeof(uint32_t)), o_tab = carve(sizeof(TableDev));
+    void *mem = nullptr;
+    if (hipMalloc(&mem, off) != hipSuccess) return fail(CSDR_ENOMEM, "%zu bytes", off);
+    std::unique_ptr<void, void (*)(void *)> guard(mem, [](void *p) { (void)hipFree(p); });
+    char *base = (char *)mem;
+    hipStream_t st = c->lanes[LANE_AUDIO];
+    const BlockPlan plan[2] = {{0, 0}, {n, n}};
+    float rec[2 * kDigStateFloats] = {state->r[0], state->r[1], state->x_hat[0], state->x_hat[1]};
+    TableJob j{};
+    j.iq = (const float2 *)(base + o_iq); j.n = n; j.nb = 1; j.plan = (const BlockPlan *)(base + o_plan);
+    j.sym = (uint32_t *)(base + o_sym); j.bevm = (float *)(base + o_bevm);
+    j.st_rd = (const float *)(base + o_st); j.st_wr = (float *)(base + o_st) + kDigStateFloats; j.tab = (const TableDev *)(base + o_tab);
+    CSDR_HIP_TRY(hipMemcpyAsync(base + o_job, &j, sizeof j, hipMemcpyHostToDevice, st));
+    CSDR_HIP_TRY(hipMemcpyAsync(base + o_plan, plan, sizeof plan, hipMemcpyHostToDevice, st));
+    CSDR_HIP_TRY(hipMemcpyAsync(base + o_st, rec, sizeof rec, hipMemcpyHostToDevice, st));
+    CSDR_HIP_TRY(hipMemcpyAsync(base + o_tab, &th, sizeof th, hipMemcpyHostToDevice, st));
+    if (n) CSDR_HIP_TRY(hipMemcpyAsync(base + o_iq, iq_host, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, st));
+    const int gx = std::max(1, (n + kTabThreads - 1) / kTabThreads);
+    CSDR_LAUNCH(c, LANE_AUDIO, KID_DIGITAL, table_demod, dim3(gx, 1), dim3(kTabThreads), sizeof(TableDev), (const TableJob *)(base + o_job));
+    CSDR_HIP_TRY(hipGetLastError());
+    float evm = 0.0f;
+    if (n) CSDR_HIP_TRY(hipMemcpyAsync(sym_host, base + o_sym, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CSDR_HIP_TRY(hipMemcpyAsync(rec, base + o_st, sizeof rec, hipMemcpyDeviceToHost, st));
+    CSDR_HIP_TRY(hipMemcpyAsync(&evm, base + o_bevm, sizeof evm, hipMemcpyDeviceToHost, st));
+    CSDR_HIP_TRY(hipStreamSynchronize(st));
+    if (n > 0) {
+        const float *w = rec + kDigStateFloats;
+        state->r[0] = w[0]; state->r[1] = w[1]; state->x_hat[0] = w[2]; state->x_hat[1] = w[3];
+    }
+    *n_symbols = n;
     if (evm_last) *evm_last = evm;
     return CSDR_OK;
 }

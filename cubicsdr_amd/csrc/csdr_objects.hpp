@@ -130,6 +130,8 @@ struct csdr_bank {
     std::vector<char> dig_jobs_h;
     DevBuf<GmskJob> gmsk_jobs;               // the GMSK slots' launch records
     std::vector<GmskJob> gmsk_jobs_h;
+    DevBuf<TableJob> tab_jobs;               // the table slots' launch records
+    std::vector<TableJob> tab_jobs_h;
 };
 
 // internal modem id: NCO + msresamp only, no modem / audio stage (the zoomed spectrum view's shift + resample, SpectrumVisualProcessor.cpp:306-379)

@@ -566,6 +566,76 @@ inline std::vector<float> gmsk_rx_taps(unsigned k, unsigned m, float bt_f) {
     return h;
 }
 
+// ---- the ring description of an APSK constellation from its points (liquid's modemcf APSK objects: concentric rings of evenly spaced points,
+// a slicer on |x| midway between neighbouring rings, a symbol map) -- csdr_design_rings, include/csdr_hip.h.  No liquid table enters: the caller
+// supplies what modemcf_modulate returns.
+struct RingPlan {
+    int n_rings = 0;
+    int size[8] = {0};
+    float radius[8] = {0}, phase[8] = {0}, slicer[8] = {0};
+    unsigned char map[256] = {0};          // symbol -> ring-ordered index
+};
+// false: not 2^k points in 2 .. 256, more than 8 rings, duplicate points, or rings that are not concentric and evenly spaced
+inline bool design_rings(const float *pts, int n, RingPlan *out) {
+    if (!pts || n < 2 || n > 256 || (n & (n - 1))) return false;
+    constexpr double kTwoPi = 6.28318530717958647692, kRadTol = 1e-4, kArgTol = 1e-4;
+    std::vector<double> rad((size_t)n);
+    std::vector<int> order((size_t)n);
+    double rmax = 0.0;
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(pts[2 * i]) || !std::isfinite(pts[2 * i + 1])) return false;
+        rad[i] = std::hypot((double)pts[2 * i], (double)pts[2 * i + 1]);
+        rmax = std::max(rmax, rad[i]);
+        order[i] = i;
+    }
+    if (!(rmax > 0.0)) return false;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return rad[a] < rad[b]; });
+    RingPlan r;
+    int base = 0;
+    for (int a = 0; a < n;) {
+        int e = a + 1;
+        while (e < n && rad[order[e]] - rad[order[a]] <= kRadTol * rmax) ++e;
+        if (r.n_rings == 8) return false;
+        const int l = r.n_rings++, p = e - a;
+        double sum = 0.0;
+        for (int q = a; q < e; ++q) sum += rad[order[q]];
+        r.size[l] = p;
+        r.radius[l] = (float)(sum / p);
+        if (sum / p <= kRadTol * rmax) {          // the centre: one point, phase 0
+            if (p != 1) return false;
+            r.phase[l] = 0.0f;
+            r.map[order[a]] = (unsigned char)base;
+        } else {
+            std::vector<double> arg((size_t)p);
+            double ph = kTwoPi;
+            for (int q = 0; q < p; ++q) {
+                const int i = order[a + q];
+                double t = std::atan2((double)pts[2 * i + 1], (double)pts[2 * i]);
+                if (t < 0.0) t = t > -1e-6 ? 0.0 : t + kTwoPi;
+                arg[q] = t;
+                ph = std::min(ph, t);
+            }
+            const double step = kTwoPi / p;
+            bool seen[256] = {false};
+            for (int q = 0; q < p; ++q) {
+                const double u = (arg[q] - ph) / step;
+                const long j = std::lround(u);
+                if (std::fabs(u - (double)j) * step > kArgTol) return false;
+                const int jj = (int)(j % p);
+                if (seen[jj]) return false;
+                seen[jj] = true;
+                r.map[order[a + q]] = (unsigned char)(base + jj);
+            }
+            r.phase[l] = (float)ph;
+        }
+        base += p;
+        a = e;
+    }
+    for (int l = 0; l + 1 < r.n_rings; ++l) r.slicer[l] = 0.5f * (r.radius[l] + r.radius[l + 1]);
+    *out = r;
+    return true;
+}
+
 // ---- block / channel sizing rules of the reference's SDR thread (SoapySDRThread.cpp:668-693) ---------------
 inline int optimal_channel_count(int64_t sample_rate) {
     if (sample_rate <= 500000) return 1;

@@ -14,7 +14,7 @@
 
 namespace csdr {
 
-enum DigScheme : int32_t { DIG_PSK = 0, DIG_DPSK, DIG_ASK, DIG_QAM, DIG_BPSK, DIG_QPSK, DIG_OOK, DIG_FSK, DIG_GMSK };
+enum DigScheme : int32_t { DIG_PSK = 0, DIG_DPSK, DIG_ASK, DIG_QAM, DIG_BPSK, DIG_QPSK, DIG_OOK, DIG_FSK, DIG_GMSK, DIG_TABLE };
 
 constexpr int kDigThreads = 256;
 constexpr int kDigFskMaxK = 2048;          // fskdem samples per symbol (its create rule: k <= 2^11)
@@ -203,6 +203,121 @@ CSDR_KERNEL __launch_bounds__(kDigThreads) void digital_demod(const DigJob *__re
                 float phi;
                 float2 xh;
                 (void)dig_decide(j.g, x, prev, &phi, &xh);
+                e = dig_evm(x, xh);
+            }
+            j.bevm[bb] = e;
+        }
+    }
+}
+
+// ---- table-driven constellations (ModemAPSK / ModemSQAM / ModemST; liquid's arb and APSK demodulators): the points are caller data
+// (csdr_constellation), the decision one of three rules -- the first nearest point, the same behind a fold into the first quadrant, or a ring slicer on |x| and a
+// rounded phase index within the ring.  One launch covers every table slot and block of a batch.
+constexpr int kTabThreads = 256;
+constexpr int kTabMaxPoints = 256, kTabMaxRings = 8;
+
+// one table as the kernel reads it (host-built from a csdr_constellation: csdr_digital.hip table_device); staged whole in LDS per workgroup
+struct TableDev {
+    int32_t rule, n_points, n_rings, pad;
+    float2 points[kTabMaxPoints];          // by symbol
+    float ring_slicer[kTabMaxRings];       // [n_rings - 1] used
+    float ring_phase[kTabMaxRings];
+    float ring_dphi[kTabMaxRings];         // (float)(2 pi / ring_size)
+    int32_t ring_size[kTabMaxRings];
+    int32_t ring_base[kTabMaxRings];       // points on the rings inside this one
+    uint8_t inv[kTabMaxPoints];            // ring-ordered index -> symbol
+};
+static_assert(sizeof(TableDev) % 4 == 0 && offsetof(TableDev, points) % 16 == 0 && kTabMaxPoints % 8 == 0 && sizeof(TableDev) == 16 + 8 * kTabMaxPoints + 5 * 4 * kTabMaxRings + kTabMaxPoints, "TableDev is staged as dwords");
+
+struct TableJob {
+    const float2 *iq;         // this batch's resampled IQ (n samples)
+    int32_t n, nb;            // samples, blocks of the batch
+    const BlockPlan *plan;    // [nb + 1] block starts inside the batch
+    uint32_t *sym;            // one symbol per sample
+    float *bevm;              // [nb] the EVM after each block
+    const float *st_rd;       // the deciding table's state before the batch (kDigStateFloats) ...
+    float *st_wr;             // ... and after it (the other copy)
+    const TableDev *tab;
+};
+
+// one sample's decision against the table in LDS; *xhat = points[symbol]
+__device__ __forceinline__ uint32_t table_decide(const TableDev &t, float2 x, float2 *xhat) {
+    uint32_t s = 0;
+    if (t.rule != 1) {      // the first point at the least distance; every product and sum rounded on its own
+        int np = t.n_points;
+        uint32_t quad = 0;
+        if (t.rule == 2) {  // folded into the first quadrant by the signs alone (exact), searched among the first quarter of the points
+            const bool nr = x.x < 0.0f, ni = x.y < 0.0f;
+            quad = (nr ? 2u : 0u) + (ni ? 1u : 0u);
+            x = make_float2(nr ? -x.x : x.x, ni ? -x.y : x.y);
+            np >>= 2;
+        }
+        // eight points a turn, their four LDS reads in flight together (one read a turn leaves the scan waiting on LDS latency); the array holds
+        // kTabMaxPoints whatever np is, so a turn's reads stay inside it.  Strict "<" from +inf in index order: the first of the least
+        float best = INFINITY;
+        const float4 *pt = reinterpret_cast<const float4 *>(t.points);
+        for (int i = 0; i < np; i += 8) {
+            float4 q[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q[k] = pt[(i >> 1) + k];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float px = (k & 1) ? q[k >> 1].z : q[k >> 1].x, py = (k & 1) ? q[k >> 1].w : q[k >> 1].y;
+                const float dx = x.x - px, dy = x.y - py;
+                const float d = rounded(dx * dx) + rounded(dy * dy);
+                if (i + k < np && d < best) { best = d; s = (uint32_t)(i + k); }
+            }
+        }
+        s += quad * (uint32_t)np;
+    } else {
+        constexpr double kTwoPi = 6.28318530717958647692;
+        const float rad = sqrtf(rounded(x.x * x.x) + rounded(x.y * x.y));
+        int l = t.n_rings - 1;
+        for (int i = t.n_rings - 2; i >= 0; --i) if (rad < t.ring_slicer[i]) l = i;      // the first ring whose slicer lies above
+        float th = atan2f(x.y, x.x);
+        if (th < 0.0f) th = (float)((double)th + kTwoPi);
+        const int p = t.ring_size[l];
+        int j = (int)roundf((th - t.ring_phase[l]) / t.ring_dphi[l]) % p;
+        if (j < 0) j += p;
+        s = t.inv[t.ring_base[l] + j];
+    }
+    *xhat = t.points[s];
+    return s;
+}
+
+// grid (workgroups, jobs), kTabThreads threads, sizeof(TableDev) bytes of dynamic LDS.  Workgroup x of a job stages the job's table in LDS (every
+// lane of a wave then reads the same address: a broadcast, no bank conflicts) and decides samples [x 256, + 256), one thread per sample; workgroup 0
+// also writes the per-block EVM, deciding each block's last sample again (an empty block repeats the state the object holds), as digital_demod.
+CSDR_KERNEL __launch_bounds__(kTabThreads) void table_demod(const TableJob *__restrict__ jobs) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const TableJob &j = jobs[blockIdx.y];
+    const int tid = threadIdx.x;
+    const int i0 = blockIdx.x * kTabThreads;
+    if (blockIdx.x != 0 && i0 >= j.n) return;              // (the whole workgroup: the grid is as wide as the batch's longest job)
+    {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(j.tab);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(smem);
+        for (int w = tid; w < (int)(sizeof(TableDev) / 4); w += kTabThreads) dst[w] = src[w];
+    }
+    __syncthreads();
+    const TableDev &t = *reinterpret_cast<const TableDev *>(smem);
+    const int i = i0 + tid;
+    if (i < j.n) {
+        const float2 x = j.iq[i];
+        float2 xh;
+        j.sym[i] = table_decide(t, x, &xh);
+        if (i == j.n - 1) { j.st_wr[0] = x.x; j.st_wr[1] = x.y; j.st_wr[2] = xh.x; j.st_wr[3] = xh.y; }
+    }
+    if (blockIdx.x == 0) {
+        const float2 r0 = make_float2(j.st_rd[0], j.st_rd[1]), xh0 = make_float2(j.st_rd[2], j.st_rd[3]);
+        for (int bb = tid; bb < j.nb; bb += kTabThreads) {
+            const int last = j.plan[bb + 1].j0 - 1;
+            float e;
+            if (last < 0) e = dig_evm(r0, xh0);
+            else {
+                const float2 x = j.iq[last];
+                float2 xh;
+                (void)table_decide(t, x, &xh);
                 e = dig_evm(x, xh);
             }
             j.bevm[bb] = e;

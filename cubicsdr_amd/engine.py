@@ -247,6 +247,40 @@ def gmsk_run(ctx, iq, state=None, sps=0, fdelay=0, ebf=0.0):
     return sym[:n.value].copy(), soft[:n.value].copy(), (st, hist)
 
 
+def design_rings(points, sensitivity=0.0):
+    """csdr_design_rings: the ring description (H.Constellation, rule RINGS) of an APSK constellation from its points by symbol (complex64,
+    what liquid's modemcf_modulate returns); raises CsdrError for anything that is not concentric, evenly spaced rings.  Host only."""
+    x = np.ascontiguousarray(points, dtype=np.complex64)
+    c = H.Constellation()
+    H.check(H.lib().csdr_design_rings(x.ctypes.data_as(C.c_void_p), int(x.size), C.byref(c)))
+    c.sensitivity = float(sensitivity)
+    return c
+
+
+def nearest_table(points, sensitivity=0.0, quadrant=False):
+    """an H.Constellation decided by the first nearest point (liquid's arb demodulator; V.29) from its points by symbol; quadrant = True: behind
+    a fold into the first quadrant (liquid's SQAM demodulators)"""
+    x = np.ascontiguousarray(points, dtype=np.complex64)
+    if x.size > H.CSDR_TABLE_MAX_POINTS:
+        raise ValueError("a constellation holds at most %d points" % H.CSDR_TABLE_MAX_POINTS)
+    c = H.Constellation()
+    c.rule, c.n_points, c.sensitivity = H.CSDR_TABLE_QUADRANT if quadrant else H.CSDR_TABLE_NEAREST, int(x.size), float(sensitivity)
+    C.memmove(c.points, x.ctypes.data, x.nbytes)
+    return c
+
+
+def table_run(ctx, table, iq, state=None):
+    """csdr_table_run: the table kernel alone on `iq` (complex64) through one modem object whose state is `state` (an H.DigitalState, updated in
+    place; None = a fresh object).  Returns (symbols uint32, evm after the last sample, state)."""
+    x = np.ascontiguousarray(iq, dtype=np.complex64)
+    st = state if state is not None else H.DigitalState()
+    out = np.empty(max(1, x.size), np.uint32)
+    n, evm = C.c_int(), C.c_float()
+    H.check(H.lib().csdr_table_run(ctx.h, C.byref(table), x.ctypes.data_as(C.c_void_p), int(x.size), C.byref(st),
+                                   out.ctypes.data_as(C.c_void_p), int(out.size), C.byref(n), C.byref(evm)))
+    return out[:n.value].copy(), evm.value, st
+
+
 class DemodBank:
     """N demodulator slots (csdr_bank); one slot = one DemodulatorInstance's Pre + Demod thread arithmetic."""
 
@@ -270,6 +304,14 @@ class DemodBank:
         p = H.DemodParams(H.CSDR_MODEM_DIGITAL, int(bandwidth), int(audio_sample_rate), 0, int(frequency))
         d = digital_params(k, cons, bps, sps, bw if ebf is None else ebf, fdelay)
         H.check(self._l.csdr_bank_configure_digital_slot(self.h, int(slot), C.byref(p), C.byref(d), post.h))
+
+    def configure_table(self, slot, post, tables, bandwidth, frequency, audio_sample_rate=48000):
+        """a table-driven digital modem (APSK, SQAM, V.29, liquid's arb family): `tables` is one H.Constellation or a sequence of up to eight with
+        distinct sizes (design_rings / nearest_table), the first active; set_digital_cons(slot, n_points) switches among them"""
+        tabs = [tables] if isinstance(tables, H.Constellation) else list(tables)
+        arr = (H.Constellation * max(1, len(tabs)))(*tabs)
+        p = H.DemodParams(H.CSDR_MODEM_DIGITAL, int(bandwidth), int(audio_sample_rate), 0, int(frequency))
+        H.check(self._l.csdr_bank_configure_table_slot(self.h, int(slot), C.byref(p), arr, len(tabs), post.h))
 
     def set_digital_cons(self, slot, cons):
         """writeSetting("cons"): the next execute decides with constellation `cons`; every constellation keeps its own state"""

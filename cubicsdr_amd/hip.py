@@ -19,6 +19,9 @@ CSDR_MODEM_DIGITAL = 10
 CSDR_DIGITAL_PSK, CSDR_DIGITAL_DPSK, CSDR_DIGITAL_ASK, CSDR_DIGITAL_QAM, CSDR_DIGITAL_BPSK, CSDR_DIGITAL_QPSK, CSDR_DIGITAL_OOK, CSDR_DIGITAL_FSK = range(8)
 CSDR_DIGITAL_GMSK = 8
 DIGITAL_BY_NAME = {"PSK": 0, "DPSK": 1, "ASK": 2, "QAM": 3, "BPSK": 4, "QPSK": 5, "OOK": 6, "FSK": 7, "GMSK": 8}
+CSDR_DIGITAL_TABLE = 9
+CSDR_TABLE_NEAREST, CSDR_TABLE_RINGS, CSDR_TABLE_QUADRANT = 0, 1, 2
+CSDR_TABLE_MAX_POINTS, CSDR_TABLE_MAX_RINGS, CSDR_TABLE_MAX_TABLES = 256, 8, 8
 CSDR_DIGITAL_MAX_CARRY = 2048
 CSDR_IQ_CF32, CSDR_IQ_CS16, CSDR_IQ_CS8, CSDR_IQ_CU8, CSDR_IQ_CS12 = range(5)
 IQ_FORMAT_BY_NAME = {"CF32": 0, "CS16": 1, "CS8": 2, "CU8": 3, "CS12": 4}
@@ -53,6 +56,13 @@ class GmskState(C.Structure):
 class DigitalState(C.Structure):
     _fields_ = [("r", C.c_float * 2), ("x_hat", C.c_float * 2), ("phi", C.c_float), ("n_carry", C.c_int32),
                 ("reserved", C.c_int32 * 2), ("carry", C.c_float * (2 * CSDR_DIGITAL_MAX_CARRY))]
+
+
+class Constellation(C.Structure):
+    _fields_ = [("rule", C.c_int32), ("n_points", C.c_int32), ("sensitivity", C.c_float), ("n_rings", C.c_int32),
+                ("points", C.c_float * (2 * CSDR_TABLE_MAX_POINTS)), ("ring_size", C.c_int32 * CSDR_TABLE_MAX_RINGS),
+                ("ring_radius", C.c_float * CSDR_TABLE_MAX_RINGS), ("ring_phase", C.c_float * CSDR_TABLE_MAX_RINGS),
+                ("ring_slicer", C.c_float * CSDR_TABLE_MAX_RINGS), ("ring_map", C.c_uint8 * CSDR_TABLE_MAX_POINTS)]
 
 
 class IqFormat(C.Structure):
@@ -211,6 +221,9 @@ ABI = {
     "csdr_ingest_set_format": (_i, [_p, C.POINTER(IqFormat)]),
     "csdr_iq_convert": (_i, [_p, C.POINTER(IqFormat), _p, _i64, _i, _p]),
     "csdr_gmsk_run": (_i, [_p, C.POINTER(DigitalParams), _p, _i, C.POINTER(GmskState), _p, _p, _p, _i, C.POINTER(_i)]),
+    "csdr_design_rings": (_i, [_p, _i, C.POINTER(Constellation)]),
+    "csdr_bank_configure_table_slot": (_i, [_p, _i, C.POINTER(DemodParams), C.POINTER(Constellation), _i, _p]),
+    "csdr_table_run": (_i, [_p, C.POINTER(Constellation), _p, _i, C.POINTER(DigitalState), _p, _i, C.POINTER(_i), C.POINTER(_f)]),
 }
 
 _lib = None

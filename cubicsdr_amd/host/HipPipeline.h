@@ -242,6 +242,9 @@ public:
         if (iqIn) iqIn->flush();
     }
     std::atomic<long long> blocksProcessed{0};
+    // the bank behind the demodulators (null before the first block): for reading a block's results beyond what the instances publish -- a digital
+    // slot's symbols, say -- while this thread waits for its next input (a handle is used from one thread at a time)
+    csdr_bank *bank() const { return bank_; }
     CsdrErrorLog errlog;                                       // failures of the device library inside run(): counted, never thrown
 
     // SDRPostThreadChannelizerType (SDRPostThread.h:9-12, setChannelizerType :142-149): takes effect at the next block,
@@ -313,6 +316,7 @@ private:
             csdr_demod_params p{};
             csdr_digital_params dp{};
             int newCons = 0;
+            const std::vector<csdr_constellation> *tables = nullptr;       // a table-driven modem's constellations (they live as long as the registry)
             {
                 std::lock_guard<std::mutex> g(d->mu_);
                 rebuild = d->dirty_ || d->builtRate_ != chanRate;
@@ -320,6 +324,7 @@ private:
                 p.modem_arg = d->modem_ ? d->modem_->csdrModemArg() : 0;
                 p.frequency = d->getFrequency();
                 if (ModemDigital *md = dynamic_cast<ModemDigital *>(d->modem_.get())) { dp = md->csdrDigitalParams(); newCons = md->csdrDigitalCons(); }
+                if (ModemDigitalTableBase *mt = dynamic_cast<ModemDigitalTableBase *>(d->modem_.get())) tables = &mt->csdrTables();
                 if (rebuild && inRange) {
                     d->dirty_ = false; d->builtRate_ = chanRate;
                     if (d->modem_ && (p.modem == CSDR_MODEM_HOST || p.modem == CSDR_MODEM_DIGITAL)) {   // DemodulatorWorkerThread.cpp:63-76: a fresh kit per (re)build
@@ -330,7 +335,15 @@ private:
             }
             if (!inRange) { (void)csdr_bank_set_active(bank_, d->slot(), 0); continue; }
             if (p.modem == CSDR_MODEM_DIGITAL) {
-                if (rebuild) { CSDR_STAGE_TRY(csdr_bank_configure_digital_slot(bank_, d->slot(), &p, &dp, post_), "csdr_bank_configure_digital_slot"); d->appliedCons_ = dp.cons; }
+                if (rebuild && tables) {            // ModemAPSK / ModemSQAM / ModemST: every table up front, the default one active
+                    CSDR_STAGE_TRY(csdr_bank_configure_table_slot(bank_, d->slot(), &p, tables->data(), (int)tables->size(), post_), "csdr_bank_configure_table_slot");
+                    d->appliedCons_ = (*tables)[0].n_points;
+                    if (newCons && newCons != d->appliedCons_) {
+                        CSDR_STAGE_TRY(csdr_bank_set_digital_cons(bank_, d->slot(), newCons), "csdr_bank_set_digital_cons");
+                        d->appliedCons_ = newCons;
+                    }
+                }
+                else if (rebuild) { CSDR_STAGE_TRY(csdr_bank_configure_digital_slot(bank_, d->slot(), &p, &dp, post_), "csdr_bank_configure_digital_slot"); d->appliedCons_ = dp.cons; }
                 else if (newCons && newCons != d->appliedCons_) {          // writeSetting("cons"): updateDemodulatorCons, no rebuild
                     CSDR_STAGE_TRY(csdr_bank_set_digital_cons(bank_, d->slot(), newCons), "csdr_bank_set_digital_cons");
                     d->appliedCons_ = newCons;

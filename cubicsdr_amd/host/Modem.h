@@ -11,6 +11,7 @@
 // signatures, so DemodulatorInstance and the GUI's modem menus bind unchanged.
 #pragma once
 #include <atomic>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -117,6 +118,8 @@ public:
     static void registerBuiltins();
     static void registerDigitalLab();        // ModemDigital.h: the digital lab's modems (the reference's ENABLE_DIGITAL_LAB), opt-in
     static void registerDigitalGMSK();       // ModemDigital.h: the lab's GMSK, opt-in on its own
+    // ModemDigital.h: APSK, SQAM and ST (V.29), opt-in, their points supplied by the application's liquid through `source`
+    static int registerDigitalTables(const std::function<bool(const std::string &name, int cons, std::vector<float> &points)> &source);
 
 private:
     static ModemFactoryList &factories() { static ModemFactoryList f; return f; }

@@ -3,15 +3,19 @@
 // csdr_digital_params of the bank slot; the decisions run on the device (csdr_bank_execute).  What the reference keeps in the modem
 // object and the application reads back -- the lock (ModemDigital.cpp:43-53) and the console output (ModemDigitalOutput) -- stays here:
 // SDRPostThread::finishDemod sets the lock from the block's csdr_digital_result and hands FSK's text to the output.
-// Registration is opt-in like the reference's build switch: Modem::registerDigitalLab(), and Modem::registerDigitalGMSK() for GMSK.  APSK, SQAM
-// and ST (V.29) are not built; they remain available as host plug-ins through Modem::addModemFactory.
+// Registration is opt-in like the reference's build switch: Modem::registerDigitalLab(), Modem::registerDigitalGMSK() for GMSK, and
+// Modem::registerDigitalTables(source) for APSK, SQAM and ST (V.29), whose points are liquid's own tables: the application, which has liquid
+// linked, supplies them through a ConstellationSource, and the device decides with them as caller data.
 #pragma once
 #include <atomic>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
+#include <functional>
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "Modem.h"
 
@@ -218,6 +222,91 @@ private:
     std::atomic<int> sps_{4}, fdelay_{3};                                                  // ModemGMSK.cpp:7-10
     std::atomic<float> ebf_{0.3f};
 };
+
+// ---- ModemAPSK / ModemSQAM / ModemST: constellations that are liquid's own tables.  The application implements a ConstellationSource with its
+// liquid -- (modem name, cons) -> the cons points modemcf_modulate returns for the symbols 0 .. cons - 1, interleaved complex; false: it has none --
+// and Modem::registerDigitalTables asks it for every table of every name ONCE, as the reference's constructors create every modemcf object up
+// front (ModemAPSK.cpp:6-15).  APSK tables go through csdr_design_rings, SQAM decides nearest-point behind its quadrant fold, ST nearest-point.
+typedef std::function<bool(const std::string &name, int cons, std::vector<float> &points)> ConstellationSource;
+
+enum { CSDR_HOST_TABLE_APSK = 0, CSDR_HOST_TABLE_SQAM = 1, CSDR_HOST_TABLE_ST = 2 };
+
+class ModemDigitalTableBase : public ModemDigital {
+public:
+    // the slot's tables (csdr_bank_configure_table_slot), the default constellation first; they live as long as the registry
+    virtual const std::vector<csdr_constellation> &csdrTables() = 0;
+    csdr_digital_params csdrDigitalParams() override { csdr_digital_params p{}; p.kind = CSDR_DIGITAL_TABLE; p.cons = csdrDigitalCons(); return p; }
+};
+
+template <int WHICH>
+class ModemDigitalTable : public ModemDigitalTableBase {
+public:
+    static ModemBase *factory() { return new ModemDigitalTable<WHICH>(); }
+    static const char *modemName() { return WHICH == CSDR_HOST_TABLE_APSK ? "APSK" : (WHICH == CSDR_HOST_TABLE_SQAM ? "SQAM" : "ST"); }
+    // the "cons" options (ModemAPSK.cpp:44-51, ModemSQAM.cpp:36-37); ST has no setting: its one table is V.29's 16 points
+    static std::vector<int> consOptions() {
+        if (WHICH == CSDR_HOST_TABLE_APSK) return {4, 8, 16, 32, 64, 128, 256};
+        if (WHICH == CSDR_HOST_TABLE_SQAM) return {32, 128};
+        return {16};
+    }
+    static std::vector<csdr_constellation> &tables() { static std::vector<csdr_constellation> t; return t; }
+    // every table of this modem from the source; false (and nothing kept) when one is missing or is not what its rule needs
+    static bool loadTables(const ConstellationSource &source) {
+        std::vector<csdr_constellation> t;
+        for (int cons : consOptions()) {
+            std::vector<float> pts;
+            if (!source || !source(modemName(), cons, pts) || pts.size() != (size_t)2 * cons) return false;
+            csdr_constellation c;
+            if (WHICH == CSDR_HOST_TABLE_APSK) { if (csdr_design_rings(pts.data(), cons, &c) != CSDR_OK) return false; }
+            else {
+                std::memset(&c, 0, sizeof c);
+                c.rule = WHICH == CSDR_HOST_TABLE_SQAM ? CSDR_TABLE_QUADRANT : CSDR_TABLE_NEAREST; c.n_points = cons;
+                std::memcpy(c.points, pts.data(), pts.size() * sizeof(float));
+            }
+            c.sensitivity = 0.005f;                                  // updateDemodulatorLock(mod, 0.005f): ModemAPSK.cpp:116, ModemSQAM.cpp:78, ModemST.cpp:30
+            t.push_back(c);
+        }
+        tables() = std::move(t);
+        return true;
+    }
+    std::string getName() override { return modemName(); }
+    ModemArgInfoList getSettings() override {
+        if (WHICH == CSDR_HOST_TABLE_ST) return ModemArgInfoList();
+        ModemArgInfo a;
+        a.key = "cons"; a.name = "Constellation"; a.description = "Modem Constellation Pattern"; a.value = std::to_string(shownCons_.load());
+        for (int c : consOptions()) a.options.push_back(std::to_string(c));
+        return ModemArgInfoList{a};
+    }
+    void writeSetting(std::string setting, std::string value) override {        // updateDemodulatorCons: a pointer move, no rebuild
+        if (WHICH == CSDR_HOST_TABLE_ST || setting != "cons") return;
+        const int c = std::stoi(value);
+        shownCons_.store(c);
+        for (int v : consOptions()) if (v == c) cons_.store(c);                  // (a value outside the options leaves the object in use)
+    }
+    std::string readSetting(std::string setting) override { return (WHICH != CSDR_HOST_TABLE_ST && setting == "cons") ? std::to_string(shownCons_.load()) : ""; }
+    int csdrDigitalCons() override { return cons_.load(); }
+    const std::vector<csdr_constellation> &csdrTables() override { return tables(); }
+
+private:
+    std::atomic<int> cons_{consOptions().front()}, shownCons_{consOptions().front()};
+};
+
+typedef ModemDigitalTable<CSDR_HOST_TABLE_APSK> ModemAPSK;
+typedef ModemDigitalTable<CSDR_HOST_TABLE_SQAM> ModemSQAM;
+typedef ModemDigitalTable<CSDR_HOST_TABLE_ST> ModemST;
+
+// APSK, SQAM and ST (CubicSDR.cpp:315-328 registers them beside the others), opt-in and only with a source of their points: a name whose tables the
+// source cannot supply is not registered.  Returns the number of names registered by this call; names registered earlier keep their tables.
+inline int Modem::registerDigitalTables(const ConstellationSource &source) {
+    registerBuiltins();
+    static std::mutex mu;
+    std::lock_guard<std::mutex> g(mu);
+    int n = 0;
+    if (ModemAPSK::tables().empty() && ModemAPSK::loadTables(source)) { addModemFactory(ModemAPSK::factory, "APSK", 200000); ++n; }
+    if (ModemSQAM::tables().empty() && ModemSQAM::loadTables(source)) { addModemFactory(ModemSQAM::factory, "SQAM", 200000); ++n; }
+    if (ModemST::tables().empty() && ModemST::loadTables(source)) { addModemFactory(ModemST::factory, "ST", 200000); ++n; }
+    return n;
+}
 
 // GMSK is registered on its own (CubicSDR.cpp:321 registers it beside the others): registerDigitalLab's list stays the one it was
 inline void Modem::registerDigitalGMSK() {

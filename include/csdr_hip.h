@@ -232,7 +232,8 @@ int  csdr_bank_total_audio(csdr_bank *bank, int64_t *n);
  * k = rate / sps samples for FSK (ModemFSK.cpp:127-143, the samples short of a symbol carried to the next block).  No audio: n_audio, level
  * and peak of its csdr_block_result stay 0.  GMSK (ModemGMSK.cpp:116-134) runs gmskdem per sps samples of each block as the reference frames them:
  * I = ceil((c + n) / sps / sps) symbols from the block's start, c = kit->inputBuffer.size() (samples past the block's end read as zero).
- * Not built: APSK, SQAM and V.29 (ModemST), whose point tables are liquid's own. */
+ * APSK, SQAM and V.29 (ModemST) -- and liquid's whole `arb` family -- run as TABLE slots (below): their points are liquid's own tables, which the
+ * product does not carry; the caller, who has liquid linked, reads them through modemcf_modulate and hands them over as data. */
 #define CSDR_MODEM_DIGITAL 10        /* configured only through csdr_bank_configure_digital_slot */
 #define CSDR_DIGITAL_PSK   0         /* ModemPSK   modemcf PSK2..PSK256, lock at EVM <= 0.005 */
 #define CSDR_DIGITAL_DPSK  1         /* ModemDPSK  modemcf DPSK2..DPSK256, 0.005 */
@@ -243,6 +244,7 @@ int  csdr_bank_total_audio(csdr_bank *bank, int64_t *n);
 #define CSDR_DIGITAL_OOK   6         /* ModemOOK, 0.005 */
 #define CSDR_DIGITAL_FSK   7         /* ModemFSK   fskdem(bps, rate / sps, bw); no lock (the reference never updates it) */
 #define CSDR_DIGITAL_GMSK  8         /* ModemGMSK  gmskdem(sps, fdelay, ebf); no lock; cons reported as 2 */
+#define CSDR_DIGITAL_TABLE 9         /* ModemAPSK / ModemSQAM / ModemST: a caller-supplied constellation; only through csdr_bank_configure_table_slot */
 
 typedef struct csdr_digital_params {
     int32_t kind;              /* CSDR_DIGITAL_* (the reference class) */
@@ -319,6 +321,65 @@ CSDR_STATIC_ASSERT(sizeof(csdr_digital_params) == 32 && offsetof(csdr_digital_pa
 CSDR_STATIC_ASSERT(sizeof(csdr_digital_result) == 32 && offsetof(csdr_digital_result, carry) == 16, "csdr_digital_result layout");
 CSDR_STATIC_ASSERT(sizeof(csdr_digital_state) == 32 + 8 * CSDR_DIGITAL_MAX_CARRY && offsetof(csdr_digital_state, carry) == 32, "csdr_digital_state layout");
 CSDR_STATIC_ASSERT(sizeof(csdr_gmsk_state) == 16, "csdr_gmsk_state layout");
+
+/* ---- table-driven constellations (ModemAPSK.cpp, ModemSQAM.cpp, ModemST.cpp; liquid's modemcf_create_arbitrary and its APSK objects)
+ * The points are caller data, numbered by symbol: what modemcf_modulate returns for s = 0 .. n_points - 1.  Three decision rules, per sample x:
+ *   CSDR_TABLE_NEAREST  modemcf_demodulate_arb (the arb family and V.29): the FIRST s that minimises |x - points[s]|^2, every operation rounded
+ *                       in float32.
+ *   CSDR_TABLE_QUADRANT modemcf_demodulate_sqam32 / _sqam128: q = 2 (re < 0) + (im < 0); x is folded into the first quadrant by those signs
+ *                       (re and im negated where negative: exact); the first nearest point s' among the first n_points / 4, as above; the symbol is
+ *                       s' + q n_points / 4.  The table must have that structure: points[s' + n_points / 4] = conj(points[s']), [s' + 2 n_points / 4] =
+ *                       -conj, [s' + 3 n_points / 4] = -points[s'], bit for bit.  Off the axes this decides as NEAREST does, except for samples so
+ *                       small that x - points[s] rounds to -points[s] in float32: there NEAREST sees four equal distances and takes the first, the
+ *                       fold still follows the signs -- and such samples do occur (a front-end's first outputs after a reset).
+ *   CSDR_TABLE_RINGS    modemcf_demodulate_apsk: rad = sqrtf(x.re^2 + x.im^2); the ring l is the first with rad < ring_slicer[l], else the last;
+ *                       theta = atan2f(im, re), plus 2 pi when negative; j = roundf((theta - ring_phase[l]) / (float)(2 pi / ring_size[l])) reduced by
+ *                       the true modulo ring_size[l]; the symbol is the s with ring_map[s] = ring_size[0] + .. + ring_size[l - 1] + j.
+ *                       (liquid casts a negative j to unsigned before its modulo; with a ring phase of 0 -- every table of liquid -- theta is never
+ *                       negative and that path never runs, so a table with other phases has no reference behaviour to differ from.)
+ * Either way x_hat = points[s], the EVM is |x_hat - x| of the block's last decided sample and the lock is evm <= sensitivity, as for the
+ * other constellations. */
+#define CSDR_TABLE_NEAREST    0
+#define CSDR_TABLE_RINGS      1
+#define CSDR_TABLE_QUADRANT   2
+#define CSDR_TABLE_MAX_POINTS 256
+#define CSDR_TABLE_MAX_RINGS  8
+#define CSDR_TABLE_MAX_TABLES 8
+typedef struct csdr_constellation {
+    int32_t rule;              /* CSDR_TABLE_* */
+    int32_t n_points;          /* a power of two in 2 .. 256 (QUADRANT: 4 .. 256) */
+    float   sensitivity;       /* updateDemodulatorLock's second argument; 0 = 0.005 (what ModemAPSK, ModemSQAM and ModemST pass) */
+    int32_t n_rings;           /* RINGS: 1 .. 8; else 0 */
+    float   points[2 * CSDR_TABLE_MAX_POINTS];     /* interleaved complex, by symbol */
+    int32_t ring_size[CSDR_TABLE_MAX_RINGS];       /* RINGS: points on ring l, inner ring first; they sum to n_points */
+    float   ring_radius[CSDR_TABLE_MAX_RINGS];
+    float   ring_phase[CSDR_TABLE_MAX_RINGS];      /* argument of the ring's point of index 0 */
+    float   ring_slicer[CSDR_TABLE_MAX_RINGS];     /* [n_rings - 1] used: the radius that parts ring l from ring l + 1 */
+    uint8_t ring_map[CSDR_TABLE_MAX_POINTS];       /* symbol -> ring-ordered index (rings in order, each ring's points by phase index) */
+} csdr_constellation;
+CSDR_STATIC_ASSERT(sizeof(csdr_constellation) == 2448 && offsetof(csdr_constellation, points) == 16 && offsetof(csdr_constellation, ring_size) == 2064 &&
+                   offsetof(csdr_constellation, ring_radius) == 2096 && offsetof(csdr_constellation, ring_phase) == 2128 &&
+                   offsetof(csdr_constellation, ring_slicer) == 2160 && offsetof(csdr_constellation, ring_map) == 2192, "csdr_constellation layout");
+/* The ring description of an APSK constellation from its points alone (host only; no liquid table is needed): *out gets rule = CSDR_TABLE_RINGS,
+ * sensitivity 0, the points and the rings.  The points are sorted by radius; points whose radii exceed that of the ring's innermost point by at most
+ * 1e-4 of the largest radius form one ring; rings are ordered by radius.  A ring of radius below that tolerance holds one point and gets phase 0; any other ring's phase is its
+ * smallest argument in [0, 2 pi) (an argument within 1e-6 below 0 counts as 0), a point's index in its ring is round((arg - phase) / (2 pi / p)) mod p,
+ * every index occurs once and every point lies within 1e-4 rad of its index's place; slicers are the float midpoints of neighbouring radii.
+ * CSDR_EINVAL for anything else: a size that is not a power of two in 2 .. 256, duplicate points, more than 8 rings, rings that are not concentric
+ * and evenly spaced. */
+int  csdr_design_rings(const float *points, int n_points, csdr_constellation *out);
+/* (Re)build slot `slot` as a table-driven digital modem: p->modem must be CSDR_MODEM_DIGITAL, the rate rule is ModemDigital.cpp:21-26 (at least
+ * 500 Hz).  `tables`: 1 .. 8 constellations with distinct n_points -- the reference classes' per-"cons" modem objects, all created up front, each
+ * with its own r / x_hat state (kept in two copies, as the other constellations' records) -- of which the first is active.  CSDR_EINVAL for a
+ * table that is not well formed (rule, sizes, non-finite values, a ring_map that is no permutation, slicers that do not ascend).
+ * csdr_bank_set_digital_cons(bank, slot, n_points) switches the active table and resets nothing (CSDR_EUNSUPPORTED: no table of that size);
+ * csdr_bank_fetch_digital_results (cons = the deciding table's n_points) and csdr_bank_fetch_symbols serve these slots as any constellation. */
+int  csdr_bank_configure_table_slot(csdr_bank *bank, int slot, const csdr_demod_params *p, const csdr_constellation *tables, int n_tables,
+                                    const csdr_post *post);
+/* The table kernel alone on n caller-supplied samples, one modem object whose state is *state (r and x_hat: read, then updated); for parity
+ * checks on identical input, the counterpart of csdr_digital_run.  *n_symbols = n; *evm_last is the object's EVM afterwards. */
+int  csdr_table_run(csdr_ctx *ctx, const csdr_constellation *table, const float *iq_host, int n, csdr_digital_state *state,
+                    uint32_t *sym_host, int cap_symbols, int *n_symbols, float *evm_last);
 
 /* ------------------------------------------------------------------ SpectrumVisualProcessor (src/process/SpectrumVisualProcessor.cpp)
  * replaces: setup :140-178 (fft_create_plan(2*fftSize, FORWARD)), process :212-637 full-span view:
