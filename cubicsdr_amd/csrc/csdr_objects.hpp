@@ -11,6 +11,7 @@
 #include "kernels_chanfft.hpp"
 #include "kernels_demod.hpp"
 #include "kernels_digital.hpp"
+#include "kernels_waterfall.hpp"
 
 using namespace csdr;      // (this header is only included by the library's own translation units, all of which do the same)
 
@@ -133,6 +134,19 @@ struct csdr_bank {
     DevBuf<TableJob> tab_jobs;               // the table slots' launch records
     std::vector<TableJob> tab_jobs_h;
 };
+
+// =================================================================================================== spectrum points for device-side readers
+// The display points of a spectrum's last process, for a reader that stays in HBM (csdr_waterfall_step_spec): `reader` is made to wait for the
+// averaging lane's enqueued work by an event (no host synchronisation); after enqueueing its reads the reader calls spec_points_release, and the
+// spectrum's next process waits for them before it rewrites the buffer.  (csdr_spec.hip)
+struct SpecPointsRef {
+    csdr_ctx *ctx = nullptr;
+    const float *points = nullptr;           // [frames][F]: the y of every point
+    int F = 0, frames = 0;
+    HideDcSpan dc;                           // csdr_spec_set_hide_dc: what csdr_spec_fetch would overwrite (empty when off)
+};
+int spec_points_acquire(csdr_spec *s, hipStream_t reader, SpecPointsRef *out);
+int spec_points_release(csdr_spec *s, hipStream_t reader);
 
 // internal modem id: NCO + msresamp only, no modem / audio stage (the zoomed spectrum view's shift + resample, SpectrumVisualProcessor.cpp:306-379)
 #define CSDR_MODEM_FRONTEND_ONLY 100

@@ -76,6 +76,9 @@ struct csdr_spec {
     bool view_frame = false;                 // the frames being post-processed belong to the zoomed view
     bool fused_ok = false;                   // N = 2^17: the 512 x 256 chain with the averaging fused into the row pass exists (kernels_spec3.hpp)
     bool fused_now = false;                  // ... and this batch takes it (full-span view)
+    // a reader of `points` that stays on the device (spec_points_acquire / _release: the waterfall's quantiser on its own stream)
+    hipEvent_t ev_points_ready = nullptr, ev_points_read = nullptr;
+    bool points_reader = false;              // ev_points_read is recorded and not yet waited for
 };
 
 extern "C" int csdr_spec_create(csdr_ctx *ctx, csdr_spec **out) {
@@ -87,6 +90,8 @@ extern "C" int csdr_spec_create(csdr_ctx *ctx, csdr_spec **out) {
         CSDR_HIP_TRY(hipEventCreateWithFlags(&s->ev_fft_done[k], hipEventDisableTiming));
         CSDR_HIP_TRY(hipEventCreateWithFlags(&s->ev_avg_done[k], hipEventDisableTiming));
     }
+    CSDR_HIP_TRY(hipEventCreateWithFlags(&s->ev_points_ready, hipEventDisableTiming));
+    CSDR_HIP_TRY(hipEventCreateWithFlags(&s->ev_points_read, hipEventDisableTiming));
     *out = s.release();
     return CSDR_OK;
 }
@@ -94,10 +99,13 @@ extern "C" void csdr_spec_destroy(csdr_spec *s) {
     DeviceScope dev__(s ? s->ctx : nullptr);
     if (!s) return;
     (void)s->ctx->sync_all();
+    if (s->points_reader) (void)hipEventSynchronize(s->ev_points_read);      // (a reader on a stream that is not the context's)
     for (int k = 0; k < 2; ++k) {
         if (s->ev_fft_done[k]) (void)hipEventDestroy(s->ev_fft_done[k]);
         if (s->ev_avg_done[k]) (void)hipEventDestroy(s->ev_avg_done[k]);
     }
+    if (s->ev_points_ready) (void)hipEventDestroy(s->ev_points_ready);
+    if (s->ev_points_read) (void)hipEventDestroy(s->ev_points_read);
     s->tw4096.release(); s->tw_hi.release(); s->tw_lo.release(); s->tmp.release(); s->carry.release();
     s->blue_w.release(); s->blue_B.release(); s->blue_a.release(); s->blue_b.release(); s->twL_hi.release(); s->twL_lo.release();
     s->stage_in.release(); s->raw.release(); s->mag.release(); s->ext_w.release(); s->ext.release(); s->pairsum.release(); s->first_b.release(); s->points.release();
@@ -121,6 +129,7 @@ extern "C" int csdr_spec_setup(csdr_spec *s, int fft_size, int max_frames) {
     const int N = 2 * fft_size;                                      // SPECTRUM_VZM 2, SpectrumVisualProcessor.h:11, .cpp:145
     if (N > (1 << 22) || (npot && 2 * (int64_t)N - 1 > (1 << 22))) return fail(CSDR_EUNSUPPORTED, "internal FFT of %d points exceeds 2^22%s", N, npot ? " (the chirp-z convolution of a size that is not a power of two is twice as long)" : "");
     if (int rc = s->ctx->sync_all()) return rc;
+    if (s->points_reader) { CSDR_HIP_TRY(hipEventSynchronize(s->ev_points_read)); s->points_reader = false; }     // the buffers below may be reallocated
     s->ready = false;
     s->seq = 0; s->avg_pending[0] = s->avg_pending[1] = false; s->tmp_reader = -1;
     SpecGeom &g = s->g;
@@ -698,6 +707,10 @@ extern "C" int csdr_spec_process(csdr_spec *s, const float *iq, int iq_is_dev, i
     DeviceScope dev__(s ? s->ctx : nullptr);
     if (!s || !s->ready) return fail(CSDR_ESTATE, "spec not set up");
     if (!iq || n_blocks <= 0 || block_len <= 0) return fail(CSDR_EINVAL, "bad block arguments");
+    if (s->points_reader) {                  // a device-side reader of the previous points (spec_points_release): the averaging lane rewrites them behind it
+        CSDR_HIP_TRY(hipStreamWaitEvent(s->ctx->lanes[LANE_AVG], s->ev_points_read, 0));
+        s->points_reader = false;
+    }
     if (s->is_view) {
         if (n_blocks != 1) return fail(CSDR_EINVAL, "the zoomed view takes one process() input per call");
         return spec_process_view(s, iq, iq_is_dev, block_len);
@@ -775,26 +788,22 @@ extern "C" int csdr_spec_process(csdr_spec *s, const float *iq, int iq_is_dev, i
 // DC-spike removal on the finished points (:578-623): the bins within 2 kHz of the input centre are overwritten by their
 // mirror images just outside that span.  A few values on the host copy; integer arithmetic as in the reference.
 static void spec_hide_dc(const csdr_spec *s, float *pts) {
-    const long long centerFreq = s->center_freq, inFreq = s->input_freq;
-    const long bandwidth = s->bandwidth;
-    const long long fftSize = s->g.F;
-    const long long freqMin = centerFreq - (bandwidth / 2), freqMax = centerFreq + (bandwidth / 2);
-    const long long zeroPt = inFreq - freqMin;
-    if (!(freqMin < inFreq && freqMax > inFreq)) return;
-    const int freqRange = (int)(freqMax - freqMin);
-    const int freqStep = freqRange / (int)fftSize;
-    if (freqStep == 0) return;                                       // (the reference would divide by zero)
-    int fftStart = (int)(zeroPt / freqStep) - (2000 / freqStep);
-    int fftEnd = (int)(zeroPt / freqStep) + (2000 / freqStep);
-    if (fftEnd - fftStart < 2) { fftEnd++; fftStart--; }
-    const int numSteps = fftEnd - fftStart;
-    const int halfWay = fftStart + (numSteps / 2);
-    if ((fftEnd + numSteps / 2 + 1 < fftSize) && (fftStart - numSteps / 2 - 1 >= 0) && (fftEnd > fftStart)) {
-        int n = 1;
-        for (int i = fftStart; i < halfWay; i++) { pts[i * 2 + 1] = pts[(fftStart - n) * 2 + 1]; n++; }
-        n = 1;
-        for (int i = halfWay; i < fftEnd; i++) { pts[i * 2 + 1] = pts[(fftEnd + n) * 2 + 1]; n++; }
-    }
+    const HideDcSpan d = hide_dc_span(s->center_freq, s->input_freq, s->bandwidth, s->g.F);      // (kernels_waterfall.hpp: one statement, shared with the waterfall's quantiser)
+    for (int i = d.start; i < d.end; i++) pts[i * 2 + 1] = pts[hide_dc_source(d, i) * 2 + 1];
+}
+
+int spec_points_acquire(csdr_spec *s, hipStream_t reader, SpecPointsRef *out) {
+    if (!s || !s->ready || !out) return fail(CSDR_ESTATE, "spec not set up");
+    CSDR_HIP_TRY(hipEventRecord(s->ev_points_ready, s->ctx->lanes[LANE_AVG]));
+    CSDR_HIP_TRY(hipStreamWaitEvent(reader, s->ev_points_ready, 0));
+    out->ctx = s->ctx; out->points = s->points.p; out->F = s->g.F; out->frames = s->nf_last;
+    out->dc = s->hide_dc ? hide_dc_span(s->center_freq, s->input_freq, s->bandwidth, s->g.F) : HideDcSpan();
+    return CSDR_OK;
+}
+int spec_points_release(csdr_spec *s, hipStream_t reader) {
+    CSDR_HIP_TRY(hipEventRecord(s->ev_points_read, reader));
+    s->points_reader = true;
+    return CSDR_OK;
 }
 
 // The device keeps only the y of every display point (the x of point i is i / F in every frame, SpectrumVisualProcessor.cpp:562: half of

@@ -636,6 +636,44 @@ inline bool design_rings(const float *pts, int n, RingPlan *out) {
     return true;
 }
 
+// ---- the waterfall's colour gradient (src/util/Gradient.cpp:37-85, Gradient::generate(len)) ------------------
+// n colour stops (r, g, b interleaved) -> len entries per channel: n - 1 chunks of len / (n - 1) entries, the last one longer by the remainder; entry
+// i of a chunk is c1 + (c2 - c1) * ((float)i / (float)chunk) with every operation rounded on its own in float, clamped to [0, 1].
+// false: fewer than 2 stops or more than len + 1 (the reference divides by a chunk size of 0 there), or a null pointer.
+inline bool gradient(const float *stops, int n, int len, float *r, float *g, float *b) {
+    if (!stops || !r || !g || !b || len < 1 || n < 2 || n > len + 1) return false;
+    size_t chunk = (size_t)len / (size_t)(n - 1), p = 0;
+    float *out[3] = {r, g, b};
+    for (size_t j = 0, jmax = (size_t)n - 1; j < jmax; ++j) {
+        if (chunk * jmax < (size_t)len && j == jmax - 1) chunk += (size_t)len - chunk * jmax;
+        for (size_t i = 0; i < chunk; ++i, ++p) {
+            const float idx = (float)i / (float)chunk;
+            for (int k = 0; k < 3; ++k) {
+                const float c1 = stops[3 * j + k], c2 = stops[3 * (j + 1) + k];
+                volatile float d = c2 - c1;              // (volatile: each step is stored as a float, whatever the compiler's contraction rule)
+                volatile float m = d * idx;
+                float c = c1 + m;
+                if (c < 0.0f) c = 0.0f;
+                if (c > 1.0f) c = 1.0f;
+                out[k][p] = c;
+            }
+        }
+    }
+    return true;
+}
+// the 256-entry RGBA8 table the raster kernel reads: channel value (uint8)(c * 255.0f + 0.5f), alpha 255 (byte order r, g, b, a)
+inline bool gradient_rgba8(const float *stops, int n, uint32_t *table /*[256]*/) {
+    float r[256], g[256], b[256];
+    if (!gradient(stops, n, 256, r, g, b)) return false;
+    auto u8 = [](float c) -> uint32_t {
+        volatile float p = c * 255.0f;                   // product and sum rounded one by one
+        const float q = p + 0.5f;
+        return q >= 0.5f ? (uint32_t)(uint8_t)q : 0u;    // (a NaN stop gives a NaN entry in the reference; here it is 0)
+    };
+    for (int i = 0; i < 256; ++i) table[i] = u8(r[i]) | (u8(g[i]) << 8) | (u8(b[i]) << 16) | 0xff000000u;
+    return true;
+}
+
 // ---- block / channel sizing rules of the reference's SDR thread (SoapySDRThread.cpp:668-693) ---------------
 inline int optimal_channel_count(int64_t sample_rate) {
     if (sample_rate <= 500000) return 1;

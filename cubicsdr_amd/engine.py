@@ -1,6 +1,6 @@
 """Thin Python host objects over the C ABI (tests, bench, smoke).  Names follow the reference objects whose
 arithmetic each handle replaces: SDRPostThread (src/sdr/SDRPostThread.cpp), DemodulatorInstance's Pre/Demod
-threads + Modem (src/demod/, src/modules/modem/), SpectrumVisualProcessor (src/process/).
+threads + Modem (src/demod/, src/modules/modem/), SpectrumVisualProcessor (src/process/), WaterfallPanel (src/panel/).
 
 Inputs may be numpy complex64 arrays (host, staged by the library) or torch CUDA tensors (HBM resident, passed by
 device pointer).  No computation happens in Python; without the HIP library or a GPU everything raises.
@@ -486,6 +486,92 @@ class SpectrumProcessor:
     def close(self):
         if self.h:
             self._l.csdr_spec_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+def design_gradient(stops, length=256):
+    """Gradient::generate(length) for colour stops [[r, g, b], ...] (host only) -> (r, g, b) float32 arrays"""
+    a = np.ascontiguousarray(stops, dtype=np.float32).reshape(-1, 3)
+    r, g, b = (np.empty(max(int(length), 0), np.float32) for _ in range(3))
+    H.check(H.lib().csdr_design_gradient(a.ctypes.data_as(C.c_void_p), int(a.shape[0]), int(length), r.ctypes.data_as(C.c_void_p),
+                                         g.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+    return r, g, b
+
+
+class Waterfall:
+    """WaterfallPanel's arithmetic (csdr_waterfall): spectrum lines quantised to bytes, two ring textures, the themed RGBA picture."""
+
+    def __init__(self, ctx, fft_size, lines, max_pending=256):
+        self._l = H.lib()
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        H.check(self._l.csdr_waterfall_create(ctx.h, C.byref(self.h)))
+        self.setup(fft_size, lines, max_pending)
+
+    def setup(self, fft_size, lines, max_pending=256):
+        H.check(self._l.csdr_waterfall_setup(self.h, int(fft_size), int(lines), int(max_pending)))
+        self.fft_size, self.half, self.lines = int(fft_size), int(fft_size) // 2, int(lines)
+
+    def set_gradient(self, stops):
+        a = np.ascontiguousarray(stops, dtype=np.float32).reshape(-1, 3)
+        H.check(self._l.csdr_waterfall_set_gradient(self.h, a.ctypes.data_as(C.c_void_p), int(a.shape[0])))
+
+    def step(self, points=None, n_lines=None):
+        """points: None (repeat the previous points n_lines times), a numpy float32 array [n_lines, n] / [n], or a CUDA torch tensor of that
+        shape; returns the number of lines taken"""
+        taken = C.c_int()
+        if points is None:
+            H.check(self._l.csdr_waterfall_step(self.h, None, 0, 0, int(1 if n_lines is None else n_lines), C.byref(taken)))
+            return taken.value
+        if isinstance(points, np.ndarray):
+            a = np.ascontiguousarray(points, dtype=np.float32)
+            ptr, is_dev, shape = a.ctypes.data_as(C.c_void_p), 0, a.shape
+        else:
+            a = points.contiguous()
+            ptr, is_dev, shape = C.c_void_p(a.data_ptr()), 1, tuple(a.shape)
+        rows = 1 if len(shape) == 1 else int(shape[0])
+        H.check(self._l.csdr_waterfall_step(self.h, ptr, is_dev, int(shape[-1]), rows, C.byref(taken)))
+        self._keep = a
+        return taken.value
+
+    def step_spec(self, spec, frame0=0, n_frames=1):
+        taken = C.c_int()
+        H.check(self._l.csdr_waterfall_step_spec(self.h, spec.h, int(frame0), int(n_frames), C.byref(taken)))
+        return taken.value
+
+    def update(self):
+        H.check(self._l.csdr_waterfall_update(self.h))
+
+    @property
+    def lines_buffered(self):
+        return self._l.csdr_waterfall_lines_buffered(self.h)
+
+    def offset(self, half=0):
+        return self._l.csdr_waterfall_offset(self.h, int(half))
+
+    def fetch_index(self, half):
+        out = np.empty((self.lines, self.half), np.uint8)
+        H.check(self._l.csdr_waterfall_fetch_index(self.h, int(half), out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def fetch_rgba(self, first_row=0, n_rows=None, fetch=True):
+        """the picture [n_rows, 2 * half, 4] uint8; fetch=False renders it and leaves it on the device (device_rgba)"""
+        n_rows = self.lines - first_row if n_rows is None else n_rows
+        if not fetch:
+            H.check(self._l.csdr_waterfall_fetch_rgba(self.h, int(first_row), int(n_rows), None, 0))
+            return None
+        out = np.empty((n_rows, 2 * self.half, 4), np.uint8)
+        H.check(self._l.csdr_waterfall_fetch_rgba(self.h, int(first_row), int(n_rows), out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def device_rgba(self):
+        p = C.c_void_p()
+        H.check(self._l.csdr_waterfall_device_rgba(self.h, C.byref(p)))
+        return p.value
+
+    def close(self):
+        if self.h:
+            self._l.csdr_waterfall_destroy(self.h)
             self.h = C.c_void_p()
 
 

@@ -223,6 +223,19 @@ ABI = {
     "csdr_gmsk_run": (_i, [_p, C.POINTER(DigitalParams), _p, _i, C.POINTER(GmskState), _p, _p, _p, _i, C.POINTER(_i)]),
     "csdr_design_rings": (_i, [_p, _i, C.POINTER(Constellation)]),
     "csdr_bank_configure_table_slot": (_i, [_p, _i, C.POINTER(DemodParams), C.POINTER(Constellation), _i, _p]),
+    "csdr_waterfall_create": (_i, [_p, _pp]),
+    "csdr_waterfall_destroy": (None, [_p]),
+    "csdr_waterfall_setup": (_i, [_p, _i, _i, _i]),
+    "csdr_design_gradient": (_i, [_p, _i, _i, _p, _p, _p]),
+    "csdr_waterfall_set_gradient": (_i, [_p, _p, _i]),
+    "csdr_waterfall_step": (_i, [_p, _p, _i, _i, _i, C.POINTER(_i)]),
+    "csdr_waterfall_step_spec": (_i, [_p, _p, _i, _i, C.POINTER(_i)]),
+    "csdr_waterfall_update": (_i, [_p]),
+    "csdr_waterfall_lines_buffered": (_i, [_p]),
+    "csdr_waterfall_offset": (_i, [_p, _i]),
+    "csdr_waterfall_fetch_index": (_i, [_p, _i, _p, _i64]),
+    "csdr_waterfall_fetch_rgba": (_i, [_p, _i, _i, _p, _i64]),
+    "csdr_waterfall_device_rgba": (_i, [_p, _pp]),
     "csdr_table_run": (_i, [_p, C.POINTER(Constellation), _p, _i, C.POINTER(DigitalState), _p, _i, C.POINTER(_i), C.POINTER(_f)]),
 }
 

@@ -590,6 +590,8 @@ public:
     void setView(bool v, long long centerFreq_in, long bandwidth_in) { setView(v); setCenterFrequency(centerFreq_in); setBandwidth(bandwidth_in); }
     bool isView() { std::lock_guard<std::mutex> g(busy_run); return is_view; }
     int getDesiredInputSize() { std::lock_guard<std::mutex> g(busy_run); return fftSize ? csdr_spec_desired_input_size(spec_) : 0; }
+    // the spectrum object, for consumers that take its lines in HBM (WaterfallPanel::stepFrom); to be used from the thread that runs this processor
+    csdr_spec *handle() { return spec_; }
 
 protected:
     bool trySetup(unsigned int n) {                                                  // setup() from inside process(): no throw

@@ -44,6 +44,7 @@ typedef struct csdr_scope csdr_scope;  /* ScopeVisualProcessor's arithmetic (aud
 typedef struct csdr_mix   csdr_mix;    /* AudioThread's mixing callback, PCM conversion */
 typedef struct csdr_ingest csdr_ingest; /* page-locked block ring -> HBM, one transfer per block */
 typedef struct csdr_comm  csdr_comm;   /* one IQ stream over the GPUs of a node: RCCL over xGMI */
+typedef struct csdr_waterfall csdr_waterfall; /* WaterfallPanel's arithmetic: quantised lines, two ring textures, themed RGBA */
 
 /* ------------------------------------------------------------------ context */
 int         csdr_abi_version(void);
@@ -465,6 +466,65 @@ int  csdr_scope_fetch(csdr_scope *scope, int frame, int which, float *points_hos
 /* the audio-scope tap of a demodulator for the LAST block of the bank's last execute (DemodulatorThread.cpp:240-316), as a frame
  * whose data lies in HBM (pass it to csdr_scope_process with data_is_dev = 1); out->n == 0: nothing to show */
 int  csdr_bank_scope_frame(csdr_bank *bank, int slot, csdr_scope_frame *out);
+
+/* ------------------------------------------------------------------ WaterfallPanel (src/panel/WaterfallPanel.cpp, src/util/Gradient.cpp)
+ * replaces: setup :13-24, setPoints :39-49, step :51-83, update :85-159, refreshTheme :26-37 with Gradient::generate (Gradient.cpp:37-85), and
+ * the unscaled picture of drawPanelContents :161-219; fed as WaterfallCanvas::processInputQueue feeds it (src/visual/WaterfallCanvas.cpp:89-126).
+ * The display points of a spectrum stay in HBM from csdr_spec_process to the coloured picture; scaling and filtering to a viewport stay with the GUI.
+ * All work of a waterfall runs on a stream of its own; the calls that return data to the host synchronise it.
+ *
+ * 1. Quantiser (:64-72).  wv = v < 0 ? 0 : (v > 0.99 ? 0.99 : v), stored to a float, then (unsigned char)floor(wv * 255.0).  The comparison with
+ *    0.99 is made in double, the clamp value becomes (float)0.99: the highest index is 252, for 0.99f, 1.0, +inf and everything between.  -0.0 and
+ *    every negative give 0.  A NaN has no defined result in the reference (the conversion is undefined); THE LIBRARY'S OWN DEFINITION is 0.
+ * 2. Lines and halves.  half = fft_size / 2 (integer division); byte i of half j comes from point j * half + i (:65-67); with an odd fft_size the
+ *    last point is not drawn, as in the reference.  A line of 2 * fft_size floats is the (x, y) pairs of SpectrumVisualData and its y values are
+ *    used (:40-45); a line of fft_size floats is used as it stands (:47); any other length -- or points == NULL -- leaves the previous points in
+ *    place and the step repeats them, which is what WaterfallCanvas.cpp:106-109 does with a frame of the wrong size.  After a setup the points
+ *    are those of before (:18-20: resized to fft_size, new ones zero).
+ * 3. Texture life cycle.  setup clears lines_buffered and marks the textures uninitialised (:16, :22-23).  Steps before the first update after a
+ *    setup are dropped (:60-62; *taken = 0; their points are still kept, setPoints does not depend on the textures).  The first update after a
+ *    setup and at least one step call (:88-90) creates both rings zero-filled with waterfall_ofs = lines - 1 (:92-130).  A call that would make
+ *    more than max_pending lines wait for an update is refused as a whole with CSDR_ERANGE: nothing is taken, nothing changes.
+ * 4. update is :132-158 literally: the pending lines are reversed (newest first) and written in runs of min(lines_buffered, waterfall_ofs[0]) rows
+ *    at rows [ofs - run, ofs); after each run ofs -= run, and an offset that reaches 0 becomes `lines`.  Two consequences are the reference's and
+ *    are kept: row lines - 1 is not written during the first turn of the ring, and when one update crosses the wrap the older remainder lands
+ *    above the newer run.  lines = 7: step A, B, C, update -> rows 3, 4, 5 hold C, B, A, ofs = 3; step D, E, F, G, H, update -> rows 0 .. 6 hold
+ *    H, G, F, C, B, E, D, ofs = 5.  (lines >= 2: with one line the reference's loop never ends.)
+ * 5. Gradient (Gradient.cpp:37-85).  n colour stops -> len entries: chunk_size = len / (n - 1), the last chunk takes the remainder; per entry
+ *    idx = (float)i / (float)chunk_size, then c1 + (c2 - c1) * idx in float with each operation rounded on its own, then a clamp to [0, 1].
+ *    2 <= n_colors <= len + 1, anything else is CSDR_EINVAL (chunk_size 0 divides by zero in the reference).  The stops are CALLER DATA, r, g, b
+ *    interleaved: the library carries no theme of the reference; the application passes what it reads from its own ColorTheme.  GL's conversion of
+ *    the mapped float to a texel is implementation-defined; THE LIBRARY'S OWN DEFINITION is (uint8)(c * 255.0f + 0.5f) per channel (product and
+ *    sum rounded one by one), alpha 255, computed once per set_gradient on the host: the device table is 256 x RGBA8 (bytes r, g, b, a).  Before
+ *    any set_gradient the table is the grey ramp i -> (i, i, i, 255).  The table outlives a setup.
+ * 6. fetch_rgba is the picture drawPanelContents shows, unscaled (:186-213: the texture coordinate t runs from waterfall_ofs / lines under
+ *    GL_REPEAT): image row r is ring row (ofs + first_row + r) mod lines of half 0 followed by the same row of half 1, 2 * half pixels of 4 bytes,
+ *    each coloured through the table; first_row >= 0, n_rows >= 1, first_row + n_rows <= lines.  out_u8 == NULL leaves the picture on the device;
+ *    csdr_waterfall_device_rgba returns the last rendered picture ([n_rows][2 * half] RGBA8, dense) and makes the context's boundary stream wait
+ *    for it, so a consumer enqueued there reads the finished picture.  It stays valid until the next fetch_rgba or setup.
+ * 7. step_spec takes frames frame0 .. frame0 + n_frames - 1 of the spectrum's last csdr_spec_process straight from its point buffer in HBM, ordered
+ *    behind the averaging lane's work by an event (no host synchronisation; the spectrum's next process in turn waits for these reads).  With
+ *    csdr_spec_set_hide_dc on it applies the DC-spike overwrite exactly as csdr_spec_fetch does.  A spectrum whose fftSize is not the waterfall's
+ *    fft_size is a frame of the wrong size (item 2).  What csdr_spec_fetch returns is not changed by it. */
+int  csdr_waterfall_create(csdr_ctx *ctx, csdr_waterfall **out);
+void csdr_waterfall_destroy(csdr_waterfall *wf);
+int  csdr_waterfall_setup(csdr_waterfall *wf, int fft_size, int lines, int max_pending);     /* setup(fft_size_in, num_waterfall_lines_in); fft_size 2 .. 2^21 */
+/* Gradient::generate(len): r, g, b receive len floats each; host only, needs no device */
+int  csdr_design_gradient(const float *rgb_stops, int n_colors, int len, float *r, float *g, float *b);
+int  csdr_waterfall_set_gradient(csdr_waterfall *wf, const float *rgb_stops, int n_colors);  /* refreshTheme: generate(256) -> the RGBA8 table in HBM */
+/* setPoints + step for each of n_lines lines of n_floats_per_line floats (host memory, or device memory produced on the boundary stream when
+ * is_dev != 0); *taken (may be NULL) = the lines that went into the pending buffer.  Host lines are copied with hipMemcpyAsync: from page-locked
+ * memory the copy may still be in flight when the call returns, so such a buffer stays unchanged until the next synchronising call on this object
+ * (csdr_waterfall_fetch_index, csdr_waterfall_fetch_rgba with a host buffer); device lines stay unchanged until then as well */
+int  csdr_waterfall_step(csdr_waterfall *wf, const float *points, int is_dev, int n_floats_per_line, int n_lines, int *taken);
+int  csdr_waterfall_step_spec(csdr_waterfall *wf, csdr_spec *spec, int frame0, int n_frames, int *taken);
+int  csdr_waterfall_update(csdr_waterfall *wf);                                              /* WaterfallPanel::update */
+int  csdr_waterfall_lines_buffered(const csdr_waterfall *wf);
+int  csdr_waterfall_offset(const csdr_waterfall *wf, int half);                              /* waterfall_ofs[half]; -1 while there are no textures */
+/* one ring texture: lines x (fft_size / 2) bytes, rows as GL holds them (synchronises) */
+int  csdr_waterfall_fetch_index(csdr_waterfall *wf, int half, uint8_t *out_u8, int64_t cap);
+int  csdr_waterfall_fetch_rgba(csdr_waterfall *wf, int first_row, int n_rows, uint8_t *out_u8, int64_t cap);
+int  csdr_waterfall_device_rgba(csdr_waterfall *wf, const uint8_t **dev);
 
 /* ------------------------------------------------------------------ audio egress
  * csdr_mix replaces the arithmetic AND the queue rules of audioCallback (src/audio/AudioThread.cpp:88-240): sources in binding order;

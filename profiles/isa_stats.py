@@ -4,7 +4,7 @@
   python profiles/isa_stats.py csdr_spec [kernel-name-substring ...]      (unit = a file of cubicsdr_amd/csrc without .hip, or a path to any .hip)
 
 Per kernel: VGPRs / SGPRs / scratch bytes, and the instruction mix of the whole code object text: packed fp32 (v_pk_*), other vector ALU,
-64-bit integer / compare / select / move instructions (address and guard overhead), scalar ALU, LDS, global memory, waits, barriers.  The
+64-bit integer / compare / select / move instructions (address and guard overhead), scalar ALU, LDS, global memory (and how many of those accesses are 16 bytes wide: ld128 / st128), waits, barriers.  The
 kernels of the spectrum chain are bound by vector-ALU issue: these counts are what a change to their instruction stream is
 judged by before it goes to the GPU.  (Counts are static -- every instruction once, loops not weighted.)"""
 import collections
@@ -79,7 +79,7 @@ def main():
         meta[m.group(1)] = (g("vgpr_count"), g("sgpr_count"), g("private_segment_fixed_size"), g("agpr_count"))
     names = sorted(bodies)
     dem = dict(zip(names, demangle(names)))
-    cols = ["v_pk", "v_other", "v_f64", "v_mov", "v_cmp/sel", "v_addr64", "s_alu", "s_load", "s_waitcnt", "s_barrier", "s_nop", "lds", "vm_load", "vm_store", "scratch", "other"]
+    cols = ["v_pk", "v_other", "v_f64", "v_mov", "v_cmp/sel", "v_addr64", "s_alu", "s_load", "s_waitcnt", "s_barrier", "s_nop", "lds", "vm_load", "vm_store", "scratch", "other", "ld128", "st128"]
     print("%-58s %5s %5s %5s | %6s | " % ("kernel", "vgpr", "sgpr", "scr", "total") + " ".join("%9s" % c for c in cols))
     for n in names:
         short = re.sub(r"\(.*", "", dem[n]).replace("csdr::", "").replace("void ", "")
@@ -94,8 +94,12 @@ def main():
             if not re.match(r"^[a-z_0-9]+$", op):
                 continue
             cnt[classify(op)] += 1
+            if re.match(r"(global|buffer|flat)_load_dwordx4", op):          # the 16-byte accesses among vm_load / vm_store
+                cnt["ld128"] += 1
+            if re.match(r"(global|buffer|flat)_store_dwordx4", op):
+                cnt["st128"] += 1
         v, s, p, _ = meta.get(n, ("?", "?", "?", "?"))
-        print("%-58s %5s %5s %5s | %6d | " % (short[:58], v, s, p, sum(cnt.values())) + " ".join("%9d" % cnt[c] for c in cols))
+        print("%-58s %5s %5s %5s | %6d | " % (short[:58], v, s, p, sum(cnt[c] for c in cols[:16])) + " ".join("%9d" % cnt[c] for c in cols))
 
 
 if __name__ == "__main__":
