@@ -147,6 +147,7 @@ struct SpecPointsRef {
 };
 int spec_points_acquire(csdr_spec *s, hipStream_t reader, SpecPointsRef *out);
 int spec_points_release(csdr_spec *s, hipStream_t reader);
+csdr_ctx *spec_ctx(const csdr_spec *s);      // the context a spectrum was created on (csdr_spec_process_distrib checks it against the distributor's)
 
 // internal modem id: NCO + msresamp only, no modem / audio stage (the zoomed spectrum view's shift + resample, SpectrumVisualProcessor.cpp:306-379)
 #define CSDR_MODEM_FRONTEND_ONLY 100

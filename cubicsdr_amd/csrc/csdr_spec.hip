@@ -800,6 +800,7 @@ int spec_points_acquire(csdr_spec *s, hipStream_t reader, SpecPointsRef *out) {
     out->dc = s->hide_dc ? hide_dc_span(s->center_freq, s->input_freq, s->bandwidth, s->g.F) : HideDcSpan();
     return CSDR_OK;
 }
+csdr_ctx *spec_ctx(const csdr_spec *s) { return s ? s->ctx : nullptr; }
 int spec_points_release(csdr_spec *s, hipStream_t reader) {
     CSDR_HIP_TRY(hipEventRecord(s->ev_points_read, reader));
     s->points_reader = true;

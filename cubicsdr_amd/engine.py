@@ -1,6 +1,6 @@
 """Thin Python host objects over the C ABI (tests, bench, smoke).  Names follow the reference objects whose
 arithmetic each handle replaces: SDRPostThread (src/sdr/SDRPostThread.cpp), DemodulatorInstance's Pre/Demod
-threads + Modem (src/demod/, src/modules/modem/), SpectrumVisualProcessor (src/process/), WaterfallPanel (src/panel/).
+threads + Modem (src/demod/, src/modules/modem/), SpectrumVisualProcessor and FFTDataDistributor (src/process/), WaterfallPanel (src/panel/).
 
 Inputs may be numpy complex64 arrays (host, staged by the library) or torch CUDA tensors (HBM resident, passed by
 device pointer).  No computation happens in Python; without the HIP library or a GPU everything raises.
@@ -572,6 +572,77 @@ class Waterfall:
     def close(self):
         if self.h:
             self._l.csdr_waterfall_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+class Distributor:
+    """FFTDataDistributor's line cutting (csdr_distrib): the waterfall feed, cut where the block lies in HBM."""
+
+    def __init__(self, ctx, max_lines=256, fft_size=None, lines_per_second=None):
+        self._l = H.lib()
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        H.check(self._l.csdr_distrib_create(ctx.h, int(max_lines), C.byref(self.h)))
+        if fft_size is not None:
+            self.set_fft_size(fft_size)
+        if lines_per_second is not None:
+            self.set_lines_per_second(lines_per_second)
+
+    def set_fft_size(self, n):
+        H.check(self._l.csdr_distrib_set_fft_size(self.h, int(n)))
+
+    def set_lines_per_second(self, lps):
+        H.check(self._l.csdr_distrib_set_lines_per_second(self.h, int(lps)))
+
+    def try_push(self, iq, frequency, sample_rate, n_samples=None):
+        """one popped input; iq: numpy complex64 (host), a CUDA torch tensor or a DevicePointer -> (return code, lines emitted)"""
+        p, is_dev, n, keep = _as_iq_arg(iq)
+        n_lines = C.c_int()
+        rc = self._l.csdr_distrib_push(self.h, p, is_dev, int(n if n_samples is None else n_samples), int(frequency), int(sample_rate), C.byref(n_lines))
+        if rc == 0:
+            self._keep = (keep, getattr(self, "_keep", (None,))[0])      # the block may still be read until the distributor's stream has passed it
+        return rc, n_lines.value
+
+    def push(self, iq, frequency, sample_rate):
+        rc, n_lines = self.try_push(iq, frequency, sample_rate)
+        H.check(rc)
+        return n_lines
+
+    @property
+    def state(self):
+        st = H.DistribState()
+        H.check(self._l.csdr_distrib_get_state(self.h, C.byref(st)))
+        return st
+
+    def lines(self):
+        """the last push's batch where it lies: (DevicePointer over n_lines * line_len samples, n_lines, line_len)"""
+        p, n, ln = C.c_void_p(), C.c_int(), C.c_int()
+        H.check(self._l.csdr_distrib_lines(self.h, C.byref(p), C.byref(n), C.byref(ln)))
+        return DevicePointer(p.value or 0, n.value * ln.value), n.value, ln.value
+
+    def fetch_lines(self):
+        """the last push's lines -> complex64 [n_lines, line_len]"""
+        st = self.state
+        out = np.empty((st.n_lines, st.line_len), np.complex64)
+        n = C.c_int()
+        H.check(self._l.csdr_distrib_fetch_lines(self.h, out.ctypes.data_as(C.c_void_p), 2 * out.size, C.byref(n)))
+        return out[:n.value]
+
+    def fetch_buffered(self):
+        """the carried samples -> complex64 [bufferedItems]"""
+        out = np.empty(max(1, int(self.state.buffered_items)), np.complex64)
+        n = C.c_int()
+        H.check(self._l.csdr_distrib_fetch_buffered(self.h, out.ctypes.data_as(C.c_void_p), 2 * out.size, C.byref(n)))
+        return out[:n.value]
+
+    def process_into(self, spec):
+        """csdr_spec_process_distrib: the last push's lines through `spec` (a SpectrumProcessor), HBM to HBM; returns the lines it was given"""
+        H.check(self._l.csdr_spec_process_distrib(spec.h, self.h))
+        return int(self.state.n_lines)
+
+    def close(self):
+        if self.h:
+            self._l.csdr_distrib_destroy(self.h)
             self.h = C.c_void_p()
 
 

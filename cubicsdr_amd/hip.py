@@ -69,6 +69,11 @@ class IqFormat(C.Structure):
     _fields_ = [("format", C.c_int32), ("offset", C.c_float), ("full_scale", C.c_double)]
 
 
+class DistribState(C.Structure):
+    _fields_ = [("line_rate_accum", C.c_double), ("buffered_items", C.c_int64), ("buffer_offset", C.c_int64), ("buffer_max", C.c_int64),
+                ("dropped", C.c_int64), ("n_lines", C.c_int32), ("line_len", C.c_int32)]
+
+
 class P2pOp(C.Structure):
     _fields_ = [("peer", C.c_int32), ("recv", C.c_int32), ("buf", C.c_void_p), ("n_samples", C.c_int64)]
 
@@ -236,6 +241,16 @@ ABI = {
     "csdr_waterfall_fetch_index": (_i, [_p, _i, _p, _i64]),
     "csdr_waterfall_fetch_rgba": (_i, [_p, _i, _i, _p, _i64]),
     "csdr_waterfall_device_rgba": (_i, [_p, _pp]),
+    "csdr_distrib_create": (_i, [_p, _i, _pp]),
+    "csdr_distrib_destroy": (None, [_p]),
+    "csdr_distrib_set_fft_size": (_i, [_p, _i]),
+    "csdr_distrib_set_lines_per_second": (_i, [_p, _i]),
+    "csdr_distrib_push": (_i, [_p, _p, _i, _i, _i64, _i64, C.POINTER(_i)]),
+    "csdr_distrib_get_state": (_i, [_p, C.POINTER(DistribState)]),
+    "csdr_distrib_lines": (_i, [_p, _pp, C.POINTER(_i), C.POINTER(_i)]),
+    "csdr_distrib_fetch_lines": (_i, [_p, _p, _i64, C.POINTER(_i)]),
+    "csdr_distrib_fetch_buffered": (_i, [_p, _p, _i64, C.POINTER(_i)]),
+    "csdr_spec_process_distrib": (_i, [_p, _p]),
     "csdr_table_run": (_i, [_p, C.POINTER(Constellation), _p, _i, C.POINTER(DigitalState), _p, _i, C.POINTER(_i), C.POINTER(_f)]),
 }
 

@@ -10,11 +10,15 @@
 //       src/process/SpectrumVisualProcessor.h:29-58 (full-span view, peak hold, DC hiding, short-input overlap rule).
 //   FFTVisualDataThread / SpectrumVisualDataThread : the 10 ms pump threads around it (FFTDataDistributor.h holds the
 //       waterfall line pacing).
+//   DeviceFFTDataDistributor : the same line pacing on a csdr_distrib -- the lines are cut where the block lies in HBM.  Opt-in:
+//       FFTVisualDataThread::setDeviceRoute(true) and SDRPostThread::setVisualReadback(false); with both no block comes back over the link.
 #pragma once
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
+#include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -254,6 +258,11 @@ public:
     // sound output on the device: demodulators that carry an AudioMixSource hand their audio to this mixer without a host round trip
     void setAudioMixer(AudioMixer *m) { mixer_.store(m); }
     SDRPostThreadChannelizerType getChannelizerType() { return (SDRPostThreadChannelizerType)chanMode.load(); }
+    // A native-format block lives in HBM only; by default the visual queues get the widened block back on the host (processBlock), for consumers
+    // that cut it there (FFTDataDistributor).  false: no read-back -- for a waterfall thread on the device route (FFTVisualDataThread::setDeviceRoute),
+    // which reads the block where it lies.  Such a block then reaches the visual queues with an empty `data`.
+    void setVisualReadback(bool on) { visualReadback_.store(on); }
+    bool getVisualReadback() { return visualReadback_.load(); }
 
 private:
     void processBlock(SDRThreadIQData &in, const DemodulatorThreadInputQueuePtr &iqOut, const DemodulatorThreadInputQueuePtr &iqVisual) {
@@ -295,7 +304,7 @@ private:
             DemodulatorThreadIQDataPtr vis = visualBuffers_.getBuffer();
             vis->frequency = in.frequency; vis->sampleRate = in.sampleRate; vis->data = in.data;
             vis->shareDeviceCopy(in);                                               // the spectrum reads the block where the ingest put it
-            if (vis->data.empty() && in.deviceData && in.deviceSamples) {
+            if (vis->data.empty() && in.deviceData && in.deviceSamples && visualReadback_.load()) {
                 // a native-format block lives in HBM only, and this queue also feeds consumers that work on the host (the waterfall's
                 // FFTDataDistributor buffers and cuts the samples themselves): they get the widened block back -- only here, where such a
                 // consumer is bound, like the single-channel branch's read-back above
@@ -554,6 +563,7 @@ private:
     ReBuffer<DemodulatorThreadIQData> visualBuffers_{"SDRPostThreadVisualDataBuffers"};
     DemodulatorThreadIQDataPtr singleOut_;                                        // single-channel mode: the DC-corrected block
     std::atomic<AudioMixer *> mixer_{nullptr};
+    std::atomic_bool visualReadback_{true};
     std::vector<int> mixSlots_;
     std::vector<std::shared_ptr<AudioMixSource>> mixSources_;
     ModemIQData hostIq_;                                                          // a host plug-in modem's input block (modemData, DemodulatorThread.h)
@@ -567,7 +577,7 @@ public:
     void setup(unsigned int fftSize_in) {                                            // :140-178
         std::lock_guard<std::mutex> g(busy_run);
         fftSize = fftSize_in;
-        csdr_must(csdr_spec_setup(spec_, (int)fftSize, 1), "csdr_spec_setup");
+        csdr_must(csdr_spec_setup(spec_, (int)fftSize, maxFrames), "csdr_spec_setup");
         csdr_must(csdr_spec_set_average_rate(spec_, fft_average_rate), "csdr_spec_set_average_rate");
         csdr_must(csdr_spec_set_scale_factor(spec_, scaleFactor), "csdr_spec_set_scale_factor");
     }
@@ -592,11 +602,40 @@ public:
     int getDesiredInputSize() { std::lock_guard<std::mutex> g(busy_run); return fftSize ? csdr_spec_desired_input_size(spec_) : 0; }
     // the spectrum object, for consumers that take its lines in HBM (WaterfallPanel::stepFrom); to be used from the thread that runs this processor
     csdr_spec *handle() { return spec_; }
+    // frames one call may produce (1: one input per process(), the reference's cadence); a processor fed by processLines needs room for the
+    // lines of one push.  Takes effect at the next setup.
+    void setMaxFrames(int n) { std::lock_guard<std::mutex> g(busy_run); maxFrames = n < 1 ? 1 : n; }
+    // The device route's process(): the lines of the distributor's last push (csdr_distrib_push), one process() input each, read where they lie
+    // in HBM; every frame goes out as process() sends it.  Frames whose consumer queue is full are lost (the lines cannot wait: the distributor
+    // rewrites their batch).  Returns the number of frames; to be called from the thread that runs this processor.
+    int processLines(csdr_distrib *lines, int nLines, long long frequency, long long sampleRate) {
+        bool doSetup = false;
+        { std::lock_guard<std::mutex> g(busy_run); if (fftSizeChanged) { doSetup = true; fftSizeChanged = false; } }
+        if (doSetup && !trySetup(newFFTSize)) return 0;
+        std::lock_guard<std::mutex> g(busy_run);
+        if (!fftSize || nLines < 1) return 0;
+        if (!errlog.ok(csdr_spec_set_input_frequency(spec_, frequency), "csdr_spec_set_input_frequency")) return 0;
+        if (!errlog.ok(csdr_spec_set_input_rate(spec_, sampleRate), "csdr_spec_set_input_rate")) return 0;
+        if (!errlog.ok(csdr_spec_process_distrib(spec_, lines), "csdr_spec_process_distrib")) return 0;
+        const int nf = csdr_spec_frames(spec_);
+        for (int f = 0; f < nf; ++f) {
+            SpectrumVisualDataPtr out = outputBuffers.getBuffer();
+            out->spectrum_points.resize(fftSize * 2);
+            if (!errlog.ok(csdr_spec_fetch(spec_, f, out->spectrum_points.data(), (int)out->spectrum_points.size(), &out->fft_ceiling, &out->fft_floor), "csdr_spec_fetch")) return f;
+            out->spectrum_hold_points.resize(fftSize * 2);
+            int nh = 0;
+            if (!errlog.ok(csdr_spec_fetch_hold(spec_, f, out->spectrum_hold_points.data(), (int)out->spectrum_hold_points.size(), &nh), "csdr_spec_fetch_hold")) return f;
+            out->spectrum_hold_points.resize((size_t)nh);
+            out->centerFreq = centerFreq; out->bandwidth = (int)bandwidth;
+            distribute(out, NON_BLOCKING_TIMEOUT);
+        }
+        return nf;
+    }
 
 protected:
     bool trySetup(unsigned int n) {                                                  // setup() from inside process(): no throw
         std::lock_guard<std::mutex> g(busy_run);
-        if (!errlog.ok(csdr_spec_setup(spec_, (int)n, 1), "csdr_spec_setup")) return false;
+        if (!errlog.ok(csdr_spec_setup(spec_, (int)n, maxFrames), "csdr_spec_setup")) return false;
         fftSize = n;
         (void)csdr_spec_set_average_rate(spec_, fft_average_rate);
         (void)csdr_spec_set_scale_factor(spec_, scaleFactor);
@@ -638,6 +677,7 @@ private:
     csdr_spec *spec_ = nullptr;
     std::mutex busy_run;
     unsigned int fftSize = 0, newFFTSize = 0;
+    int maxFrames = 1;
     bool fftSizeChanged = false, is_view = false;
     float fft_average_rate = 0.65f, scaleFactor = 1.0f;
     long long centerFreq = 0;
@@ -645,43 +685,117 @@ private:
     ReBuffer<SpectrumVisualData> outputBuffers{"SpectrumVisualProcessorBuffers"};
 };
 
+// FFTDataDistributor's surface on a csdr_distrib: one push per popped input, the lines stay in HBM (include/csdr_hip.h, "FFTDataDistributor").
+// A block that carries deviceData is read where the ingest put it; one that does not (the single-channel branch hands on the DC-corrected
+// block it read back) is staged from its host samples.
+class DeviceFFTDataDistributor {
+public:
+    explicit DeviceFFTDataDistributor(csdr_ctx *ctx, int maxLines = 64) { csdr_must(csdr_distrib_create(ctx, maxLines, &d_), "csdr_distrib_create"); }
+    ~DeviceFFTDataDistributor() { if (d_) csdr_distrib_destroy(d_); }
+    DeviceFFTDataDistributor(const DeviceFFTDataDistributor &) = delete;
+    DeviceFFTDataDistributor &operator=(const DeviceFFTDataDistributor &) = delete;
+    void setFFTSize(unsigned int size) { if (size != fftSize_) { fftSize_ = size; (void)errlog.ok(csdr_distrib_set_fft_size(d_, (int)size), "csdr_distrib_set_fft_size"); } }
+    void setLinesPerSecond(unsigned int lines) { linesPerSecond_ = lines; (void)errlog.ok(csdr_distrib_set_lines_per_second(d_, (int)lines), "csdr_distrib_set_lines_per_second"); }
+    unsigned int getLinesPerSecond() const { return linesPerSecond_; }
+    // one popped input (FFTDataDistributor.cpp:41-143); returns the lines it emitted, -1 when the library refused the block
+    int push(const DemodulatorThreadIQData &inp) {
+        const size_t n = inp.numSamples();
+        const bool inHbm = inp.deviceData && inp.deviceSamples == n;
+        int lines = 0;
+        if (!errlog.ok(csdr_distrib_push(d_, inHbm ? inp.deviceData : (const float *)inp.data.data(), inHbm ? 1 : 0, (int)n, inp.frequency, inp.sampleRate, &lines), "csdr_distrib_push")) return -1;
+        return lines;
+    }
+    csdr_distrib *handle() { return d_; }
+    // test hooks, as on the host class
+    double lineRateAccumulator() const { csdr_distrib_state st{}; (void)csdr_distrib_get_state(d_, &st); return st.line_rate_accum; }
+    size_t buffered() const { csdr_distrib_state st{}; (void)csdr_distrib_get_state(d_, &st); return (size_t)st.buffered_items; }
+    CsdrErrorLog errlog;
+
+private:
+    csdr_distrib *d_ = nullptr;
+    unsigned int fftSize_ = DEFAULT_FFT_SIZE, linesPerSecond_ = DEFAULT_WATERFALL_LPS;
+};
+
 // The two pump threads around the spectrum path (src/process/FFTVisualDataThread.cpp:26-82: distributor -> processor for the
 // waterfall; SpectrumVisualDataThread.cpp:14-25: the processor alone), both ticking every 10 ms.
 class FFTVisualDataThread : public IOThread {
 public:
-    explicit FFTVisualDataThread(csdr_ctx *ctx) : wproc(ctx), linesPerSecond(DEFAULT_WATERFALL_LPS), lpsChanged(true) {}
+    explicit FFTVisualDataThread(csdr_ctx *ctx) : ctx_(ctx), wproc(ctx), linesPerSecond(DEFAULT_WATERFALL_LPS), lpsChanged(true) {}
     void setLinesPerSecond(int lps) { linesPerSecond.store(lps); lpsChanged.store(true); }
     int getLinesPerSecond() { return linesPerSecond.load(); }
     SpectrumVisualProcessor *getProcessor() { return &wproc; }
-    void run() override {
-        auto in = std::static_pointer_cast<DemodulatorThreadInputQueue>(getInputQueue("IQDataInput"));
-        auto out = std::static_pointer_cast<SpectrumVisualDataQueue>(getOutputQueue("FFTDataOutput"));
+    // The device route (off by default; choose it before the thread runs): every popped block goes through csdr_distrib_push ->
+    // csdr_spec_process_distrib -> one fetch per line, so the samples are cut and transformed where they lie in HBM.  maxLines bounds the lines
+    // of one block (a block that would emit more is dropped and counted in deviceDistributor()->errlog).  onDeviceLines, when set, runs after
+    // every block that made frames, on this thread, with the processor and the number of frames: WaterfallPanel::stepFrom(proc, 0, n) takes them
+    // into a device panel without a trip over the link.
+    void setDeviceRoute(bool on, int maxLines = 64) { deviceRoute_ = on; deviceMaxLines_ = maxLines < 1 ? 1 : maxLines; }
+    bool getDeviceRoute() const { return deviceRoute_; }
+    std::function<void(SpectrumVisualProcessor &, int)> onDeviceLines;
+    DeviceFFTDataDistributor *deviceDistributor() { return devDistrib_.get(); }
+    // what run() does before its loop, and one turn of the loop (run() sleeps 10 ms between turns); public so that a caller can pump the
+    // thread's objects itself, block by block
+    void bind() {
+        in_ = std::static_pointer_cast<DemodulatorThreadInputQueue>(getInputQueue("IQDataInput"));
+        out_ = std::static_pointer_cast<SpectrumVisualDataQueue>(getOutputQueue("FFTDataOutput"));
         fftQueue->set_max_num_items(100);
-        out->set_max_num_items(100);
-        fftDistrib.setInput(in);
-        fftDistrib.attachOutput(fftQueue);
-        wproc.setInput(fftQueue);
-        wproc.attachOutput(out);
+        out_->set_max_num_items(100);
+        if (deviceRoute_) {
+            devDistrib_.reset(new DeviceFFTDataDistributor(ctx_, deviceMaxLines_));
+            wproc.setMaxFrames(deviceMaxLines_);
+        } else {
+            fftDistrib.setInput(in_);
+            fftDistrib.attachOutput(fftQueue);
+            wproc.setInput(fftQueue);
+        }
+        wproc.attachOutput(out_);
         wproc.setup(DEFAULT_FFT_SIZE);
+    }
+    void pumpOnce() {
+        const int want = wproc.getDesiredInputSize();
+        const unsigned fft = want ? (unsigned)want : DEFAULT_FFT_SIZE * 2;           // SPECTRUM_VZM
+        if (deviceRoute_) {
+            devDistrib_->setFFTSize(fft);
+            if (lpsChanged.load()) { devDistrib_->setLinesPerSecond((unsigned)linesPerSecond.load()); lpsChanged.store(false); }
+            while (!stopping && !in_->empty()) {
+                if (!wproc.isOutputEmpty()) return;                                  // a consumer queue is full: try again later
+                DemodulatorThreadIQDataPtr inp;
+                if (!in_->pop(inp, HEARTBEAT_CHECK_PERIOD_MICROS) || !inp) continue;
+                const int lines = devDistrib_->push(*inp);
+                if (lines < 1) continue;
+                const int frames = wproc.processLines(devDistrib_->handle(), lines, inp->frequency, inp->sampleRate);
+                if (frames > 0 && onDeviceLines) onDeviceLines(wproc, frames);
+            }
+            return;
+        }
+        fftDistrib.setFFTSize(fft);
+        if (lpsChanged.load()) { fftDistrib.setLinesPerSecond((unsigned)linesPerSecond.load()); lpsChanged.store(false); }
+        fftDistrib.run();
+        while (!stopping && !wproc.isInputEmpty()) wproc.run();
+    }
+    void run() override {
+        bind();
         while (!stopping) {
             std::this_thread::sleep_for(std::chrono::milliseconds((int)(FFT_DISTRIBUTOR_BUFFER_IN_SECONDS * 1000.0 / 25.0)));
-            const int want = wproc.getDesiredInputSize();
-            fftDistrib.setFFTSize(want ? (unsigned)want : DEFAULT_FFT_SIZE * 2);     // SPECTRUM_VZM
-            if (lpsChanged.load()) { fftDistrib.setLinesPerSecond((unsigned)linesPerSecond.load()); lpsChanged.store(false); }
-            fftDistrib.run();
-            while (!stopping && !wproc.isInputEmpty()) wproc.run();
+            pumpOnce();
         }
-        in->flush();
-        out->flush();
+        in_->flush();
+        out_->flush();
     }
     void terminate() override { IOThread::terminate(); fftDistrib.flushQueues(); wproc.flushQueues(); }
 
 protected:
+    csdr_ctx *ctx_;
     FFTDataDistributor fftDistrib;
     DemodulatorThreadInputQueuePtr fftQueue = std::make_shared<DemodulatorThreadInputQueue>();
     SpectrumVisualProcessor wproc;
     std::atomic_int linesPerSecond;
     std::atomic_bool lpsChanged;
+    bool deviceRoute_ = false;
+    int deviceMaxLines_ = 64;
+    std::unique_ptr<DeviceFFTDataDistributor> devDistrib_;
+    DemodulatorThreadInputQueuePtr in_;
+    SpectrumVisualDataQueuePtr out_;
 };
 
 class SpectrumVisualDataThread : public IOThread {

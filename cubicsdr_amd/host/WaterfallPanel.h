@@ -81,6 +81,12 @@ public:
         staged_ = false;
         return errlog.ok(csdr_waterfall_step_spec(wf_, proc.handle(), 0, 1, nullptr), "csdr_waterfall_step_spec");
     }
+    // the lines of frames frame0 .. frame0 + nFrames - 1 of the processor's last input (SpectrumVisualProcessor::processLines makes several)
+    bool stepFrom(SpectrumVisualProcessor &proc, int frame0, int nFrames) {
+        if (!wf_) return errlog.ok(CSDR_ESTATE, "WaterfallPanel::stepFrom needs a device panel");
+        staged_ = false;
+        return errlog.ok(csdr_waterfall_step_spec(wf_, proc.handle(), frame0, nFrames, nullptr), "csdr_waterfall_step_spec");
+    }
     void update() {                                                                  // :85-159
         if (wf_) { (void)errlog.ok(csdr_waterfall_update(wf_), "csdr_waterfall_update"); return; }
         const unsigned int half_fft_size = fft_size / 2;

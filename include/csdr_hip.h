@@ -45,6 +45,7 @@ typedef struct csdr_mix   csdr_mix;    /* AudioThread's mixing callback, PCM con
 typedef struct csdr_ingest csdr_ingest; /* page-locked block ring -> HBM, one transfer per block */
 typedef struct csdr_comm  csdr_comm;   /* one IQ stream over the GPUs of a node: RCCL over xGMI */
 typedef struct csdr_waterfall csdr_waterfall; /* WaterfallPanel's arithmetic: quantised lines, two ring textures, themed RGBA */
+typedef struct csdr_distrib csdr_distrib; /* FFTDataDistributor's line cutting: the waterfall feed, cut where the block lies in HBM */
 
 /* ------------------------------------------------------------------ context */
 int         csdr_abi_version(void);
@@ -525,6 +526,62 @@ int  csdr_waterfall_offset(const csdr_waterfall *wf, int half);                 
 int  csdr_waterfall_fetch_index(csdr_waterfall *wf, int half, uint8_t *out_u8, int64_t cap);
 int  csdr_waterfall_fetch_rgba(csdr_waterfall *wf, int first_row, int n_rows, uint8_t *out_u8, int64_t cap);
 int  csdr_waterfall_device_rgba(csdr_waterfall *wf, const uint8_t **dev);
+
+/* ------------------------------------------------------------------ FFTDataDistributor (src/process/FFTDataDistributor.cpp)
+ * replaces: the ctor's defaults :11, setFFTSize :15-18, setLinesPerSecond :20-22 and, per csdr_distrib_push, ONE popped input of process() :41-143
+ * statement for statement -- the reset on a change of rate or frequency :42-53, the growth on an fft change alone :56-59, compaction and overflow
+ * :66-76, the append :79-80, the pacing arithmetic :89-96, "move along" :101-104, the accumulate / emit / wrap loop :106-129, the offset clamp
+ * :133-141.  All of that is host integer and double arithmetic in the reference's order of operations; the samples are only copied, and they are
+ * copied inside HBM: the block is read where the ingest (or the caller) put it, the lines land in a batch the spectrum reads in place
+ * (csdr_spec_process_distrib), and nothing crosses the link.
+ *
+ * 1. The buffer.  After every input fewer than fft_size samples stay buffered, so the reference's 0.25 s buffer is not kept: the device holds the
+ *    carried samples only (bufferedItems of them; after fft_size shrank there can be more than the new fft_size -- up to the largest fft_size used
+ *    so far, minus one), and a push works on the virtual stream carry ++ block.  bufferMax and bufferOffset are kept as the integers they are in
+ *    the reference, because they decide the overflow rule: when bufferOffset + bufferedItems + n_samples > bufferMax the offset returns to 0, and
+ *    if bufferedItems + n_samples still exceeds bufferMax the LAST n_samples - (bufferMax - bufferedItems) incoming samples are dropped (:66-76).
+ * 2. A line is fft_size consecutive samples of that stream starting at a multiple of fft_size; which of them go out is the accumulator's decision
+ *    (:106-129).  The reference pushes lines to its output queues without blocking and loses what does not fit (:121); here every emitted line
+ *    is in the batch, and a push that would emit more than max_lines lines is refused as a whole.
+ * 3. Refusals: CSDR_EINVAL for fft_size < 1, lines per second < 0, sample_rate <= 0, n_samples < 0 (or a null block with n_samples > 0, or a
+ *    device block that is not 8-byte aligned); CSDR_ERANGE for a push that would emit more than max_lines lines.  A refusal enqueues nothing and
+ *    leaves the state, the carried samples and both batches as they were.
+ * 4. Two batches alternate: the pointer csdr_distrib_lines returns holds the lines of the last push ([n_lines][line_len] complex samples, dense)
+ *    and stays valid, with its contents, until the second push after it.
+ * 5. Ordering.  The distributor's copies run on a stream of its own.  A device block is ordered behind its producer as csdr_spec_process orders a
+ *    device input (work enqueued on the boundary stream, the ingest's transfer), and its reads are joined to the spectrum's FFT lane, so an
+ *    ingest ring recycles the block behind them.  csdr_spec_process_distrib makes the spectrum wait for the copy by an event and leaves one the
+ *    distributor waits for before it rewrites that batch: no host synchronisation between push, spectrum and csdr_waterfall_step_spec.  (The table
+ *    of line starts is uploaded from page-locked memory that a push reuses two pushes later; it first waits for that earlier copy, long done.)
+ *    A host block (iq_is_dev = 0; for callers without an ingest) is staged as a whole with hipMemcpyAsync: from page-locked memory the copy may
+ *    still be in flight when the call returns, so such a block stays unchanged until the next synchronising call on this object (the fetches). */
+typedef struct csdr_distrib_state {
+    double  line_rate_accum;   /* lineRateAccum */
+    int64_t buffered_items;    /* bufferedItems */
+    int64_t buffer_offset;     /* bufferOffset */
+    int64_t buffer_max;        /* bufferMax */
+    int64_t dropped;           /* incoming samples the last push dropped (:71-75) */
+    int32_t n_lines;           /* lines the last push emitted */
+    int32_t line_len;          /* their length: the fft_size that push read */
+} csdr_distrib_state;
+CSDR_STATIC_ASSERT(sizeof(csdr_distrib_state) == 48 && offsetof(csdr_distrib_state, n_lines) == 40, "csdr_distrib_state layout");
+int  csdr_distrib_create(csdr_ctx *ctx, int max_lines, csdr_distrib **out);                   /* ctor :11: fft_size 2048, 30 lines per second */
+void csdr_distrib_destroy(csdr_distrib *d);
+int  csdr_distrib_set_fft_size(csdr_distrib *d, int n);                                       /* setFFTSize :15-18; read at the next push */
+int  csdr_distrib_set_lines_per_second(csdr_distrib *d, int lps);                             /* setLinesPerSecond :20-22 */
+/* one popped input (:41-143): n_samples complex samples at iq with inp->frequency and inp->sampleRate; *n_lines (may be NULL) = lines emitted */
+int  csdr_distrib_push(csdr_distrib *d, const float *iq, int iq_is_dev, int n_samples, int64_t frequency, int64_t sample_rate, int *n_lines);
+int  csdr_distrib_get_state(const csdr_distrib *d, csdr_distrib_state *st);
+int  csdr_distrib_lines(csdr_distrib *d, const float **dev_lines, int *n_lines, int *line_len); /* the last push's batch where it lies in HBM */
+/* the last push's lines / the carried samples to the host (2 floats per sample; synchronise the distributor's stream): tests, host consumers */
+int  csdr_distrib_fetch_lines(csdr_distrib *d, float *host, int64_t cap_floats, int *n_lines);
+int  csdr_distrib_fetch_buffered(csdr_distrib *d, float *host, int64_t cap_floats, int *n_samples);
+/* The last push's lines through SpectrumVisualProcessor::process, one input each, in order (the queue between the two in FFTVisualDataThread.cpp:58-70).
+ * Full-span view: ONE csdr_spec_process(dev_lines, 1, n_lines, line_len, mode) -- CSDR_SPEC_FIRST_FRAME for lines of at least
+ * csdr_spec_desired_input_size samples (what FFTVisualDataThread asks the distributor for), CSDR_SPEC_LINES for shorter ones; so the spectrum needs
+ * max_frames >= n_lines and csdr_spec_frames / csdr_spec_fetch / csdr_waterfall_step_spec see n_lines frames.  Zoomed view: one call per line
+ * (every call is one input there).  A push that emitted no line leaves the spectrum untouched.  Both handles are used by this call. */
+int  csdr_spec_process_distrib(csdr_spec *spec, csdr_distrib *d);
 
 /* ------------------------------------------------------------------ audio egress
  * csdr_mix replaces the arithmetic AND the queue rules of audioCallback (src/audio/AudioThread.cpp:88-240): sources in binding order;
