@@ -288,7 +288,7 @@ enum CsdrKernelId {
     KID_MODEM, KID_GAIN_SCAN, KID_FMS, KID_AUDIO, KID_FMS_OUT, KID_MIX, KID_TABLES,
     KID_FFT_COLS, KID_FFT_ROWS, KID_SPEC_AVG, KID_SPEC_TRACK, KID_SPEC_DISPLAY, KID_SPEC_MISC,
     KID_DIGITAL,
-    KID_WF_QUANTIZE, KID_WF_UPDATE, KID_WF_RGBA,
+    KID_WF_QUANTIZE, KID_WF_UPDATE, KID_WF_RGBA, KID_WF_VIEW_LINEAR, KID_WF_VIEW_PEAK,
     KID_DISTRIB_GATHER,
     KID_COUNT
 };

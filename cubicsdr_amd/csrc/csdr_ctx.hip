@@ -144,7 +144,7 @@ static const char *kKernelNames[KID_COUNT] = {
     "demod_modem", "demod_gain_scan", "fms_stages", "demod_audio_interp", "fms_out", "audio_egress", "bank_tables",
     "spec_fft_radix", "spec_fft_rows", "spec_average", "spec_extrema", "spec_display", "spec_misc",
     "digital_demod",
-    "wf_quantize", "wf_update", "wf_rgba",
+    "wf_quantize", "wf_update", "wf_rgba", "wf_view_linear", "wf_view_peak",
     "distrib_gather"};
 static int prof_drain(csdr_ctx *c) {
     if (int rc = c->sync_all()) return rc;

@@ -25,6 +25,13 @@ struct csdr_waterfall {
     DevBuf<uint8_t> pend, ring;                        // lineBuffer[2]: [2][max_pending][pitch]; the two textures: [2][lines][pitch]
     DevBuf<uint32_t> table, image;                     // the 256-entry RGBA8 table; the last rendered picture
     int64_t image_pixels = 0;
+    // the viewport (csdr_waterfall_render_view): tap tables per (geometry, width, height, mode) -- they do not depend on ofs -- and a picture of its own
+    DevBuf<csdr_view_tap> taps;                        // [width] columns, then [height] rows
+    std::vector<csdr_view_tap> taps_host;              // (the upload's source: stays until the next rebuild)
+    DevBuf<uint32_t> view;
+    int taps_w = 0, taps_h = 0, taps_mode = -1;        // what `taps` was designed for; taps_mode -1: nothing
+    int view_w = 0, view_h = 0;                        // the last rendered view; 0: none
+    int peak_tile[2] = {0, 0}, peak_slots = 0;         // wf_view_peak's tiling for `taps`
     uint8_t *pend_of(int j) const { return pend.p + (size_t)j * max_pending * pitch; }
     uint8_t *ring_of(int j) const { return ring.p + (size_t)j * lines * pitch; }
 };
@@ -60,7 +67,7 @@ extern "C" void csdr_waterfall_destroy(csdr_waterfall *w) {
     if (w->st) { (void)hipStreamSynchronize(w->st); (void)hipStreamDestroy(w->st); }
     if (w->ev_in) (void)hipEventDestroy(w->ev_in);
     if (w->ev_out) (void)hipEventDestroy(w->ev_out);
-    w->points.release(); w->stage.release(); w->pend.release(); w->ring.release(); w->table.release(); w->image.release();
+    w->points.release(); w->stage.release(); w->pend.release(); w->ring.release(); w->table.release(); w->image.release(); w->taps.release(); w->view.release();
     delete w;
 }
 
@@ -91,6 +98,7 @@ extern "C" int csdr_waterfall_setup(csdr_waterfall *w, int fft_size, int lines, 
     w->lines_buffered = 0;                               // :16
     w->tex_init = false; w->buffer_init = false;         // :22-23
     w->image_pixels = 0;
+    w->taps_mode = -1; w->view_w = w->view_h = 0;
     w->ready = true;
     return CSDR_OK;
 }
@@ -265,5 +273,104 @@ extern "C" int csdr_waterfall_device_rgba(csdr_waterfall *w, const uint8_t **dev
     CSDR_HIP_TRY(hipEventRecord(w->ev_out, w->st));       // whatever the caller enqueues on the boundary stream next reads the finished picture
     CSDR_HIP_TRY(hipStreamWaitEvent(w->ctx->stream, w->ev_out, 0));
     *dev = reinterpret_cast<const uint8_t *>(w->image.p);
+    return CSDR_OK;
+}
+
+// ---- the viewport: drawPanelContents (:161-219) scaled to width x height (csdr_hip.h, "Waterfall viewport") ----
+static_assert(sizeof(design::ViewTap) == sizeof(csdr_view_tap) && offsetof(design::ViewTap, frac) == offsetof(csdr_view_tap, frac) &&
+              offsetof(design::ViewTap, half) == offsetof(csdr_view_tap, half), "design::ViewTap is csdr_view_tap");
+
+extern "C" int csdr_design_view_columns(int fft_size, int width, int mode, csdr_view_tap *taps) {
+    if (!design::view_columns(fft_size, width, mode, reinterpret_cast<design::ViewTap *>(taps)))
+        return fail(CSDR_EINVAL, "view columns: fft_size %d (>= 4), width %d (2 .. 16384), mode %d, no null pointer", fft_size, width, mode);
+    return CSDR_OK;
+}
+extern "C" int csdr_design_view_rows(int lines, int height, int mode, csdr_view_tap *taps) {
+    if (!design::view_rows(lines, height, mode, reinterpret_cast<design::ViewTap *>(taps)))
+        return fail(CSDR_EINVAL, "view rows: lines %d (2 .. 2^20), height %d (1 .. 16384), mode %d, no null pointer", lines, height, mode);
+    return CSDR_OK;
+}
+
+constexpr int kWfPeakSlots = 1024;           // 16 KB of LDS for a tile's texel span: nine workgroups to a compute unit
+
+// the tap tables of (width, height, mode) on the device; for PEAK also the tiling: as many pixels to a workgroup (up to one per work-item) as keep
+// the tile's span, widened to 16-byte chunks, inside the slots -- a single pixel wider than that is a tile of its own and is folded by the kernel
+static int wf_view_tables(csdr_waterfall *w, int width, int height, int mode) {
+    if (w->taps_mode == mode && w->taps_w == width && w->taps_h == height) return CSDR_OK;
+    std::vector<csdr_view_tap> t((size_t)width + (size_t)height);
+    if (int rc = csdr_design_view_columns(w->fft_size, width, mode, t.data())) return rc;
+    if (int rc = csdr_design_view_rows(w->lines, height, mode, t.data() + width)) return rc;
+    int tile[2] = {0, 0}, slots = 1;
+    if (mode == CSDR_WF_VIEW_PEAK) {
+        const int n0 = width / 2;
+        for (int h = 0; h < 2; ++h) {
+            const int64_t nh = h ? width - n0 : n0;
+            tile[h] = (int)std::max<int64_t>(1, std::min<int64_t>(kWfThreads, ((int64_t)kWfPeakSlots * 16 - 32) * nh / w->half));
+            const csdr_view_tap *c = t.data() + (h ? n0 : 0);
+            for (int64_t k0 = 0; k0 < nh; k0 += tile[h]) {
+                const csdr_view_tap &a = c[k0], &b = c[std::min<int64_t>(k0 + tile[h], nh) - 1];
+                const int chunks = (b.first + b.count + 15) / 16 - a.first / 16;
+                if (chunks > kWfPeakSlots && tile[h] > 1) return fail(CSDR_EINVAL, "view tiling: %d chunks for %d pixels", chunks, tile[h]);
+                slots = std::max(slots, std::min(chunks, kWfPeakSlots));
+            }
+        }
+    }
+    CSDR_HIP_TRY(hipStreamSynchronize(w->st));           // a kernel or an upload may still read what is replaced
+    if (int rc = w->taps.reserve(t.size())) { w->taps_mode = -1; return rc; }
+    w->taps_host.swap(t);
+    w->taps_mode = -1;
+    CSDR_HIP_TRY(hipMemcpyAsync(w->taps.p, w->taps_host.data(), w->taps_host.size() * sizeof(csdr_view_tap), hipMemcpyHostToDevice, w->st));
+    w->taps_w = width; w->taps_h = height; w->taps_mode = mode;
+    w->peak_tile[0] = tile[0]; w->peak_tile[1] = tile[1]; w->peak_slots = slots;
+    return CSDR_OK;
+}
+
+extern "C" int csdr_waterfall_render_view(csdr_waterfall *w, int width, int height, int mode, uint8_t *out_u8, int64_t cap) {
+    DeviceScope dev__(w ? w->ctx : nullptr);
+    if (!w || !w->ready || !w->tex_init) return fail(CSDR_ESTATE, "no textures yet (setup, step, update)");         // :162-164
+    if (w->fft_size < 4 || width < 2 || width > design::kViewMaxSide || height < 1 || height > design::kViewMaxSide ||
+        (mode != CSDR_WF_VIEW_LINEAR && mode != CSDR_WF_VIEW_PEAK))
+        return fail(CSDR_EINVAL, "view %d x %d, mode %d of fft_size %d (fft_size >= 4, width 2 .. 16384, height 1 .. 16384)", width, height, mode, w->fft_size);
+    const int64_t pixels = (int64_t)width * height;
+    if (out_u8 && cap < 4 * pixels) return fail(CSDR_ERANGE, "need %lld bytes", (long long)(4 * pixels));
+    if (int rc = wf_view_tables(w, width, height, mode)) return rc;
+    if ((size_t)pixels > w->view.cap) {
+        CSDR_HIP_TRY(hipStreamSynchronize(w->st));
+        w->view_w = w->view_h = 0;                       // (the buffer csdr_waterfall_device_view handed out goes away)
+    }
+    if (int rc = w->view.reserve((size_t)pixels)) return rc;
+    WfViewArgs a{};
+    a.ring[0] = w->ring_of(0); a.ring[1] = w->ring_of(1); a.table = w->table.p;
+    a.cols = w->taps.p; a.rows = w->taps.p + width; a.out = w->view.p;
+    a.width = width; a.height = height; a.pitch = w->pitch; a.lines = w->lines; a.ofs = w->ofs[0];
+    if (mode == CSDR_WF_VIEW_LINEAR) {
+        const int groups = (width + 3) / 4;
+        const dim3 grid((unsigned)((groups + kWfThreads - 1) / kWfThreads), (unsigned)height);
+        WF_LAUNCH(w, KID_WF_VIEW_LINEAR, wf_view_linear, grid, 256 * sizeof(uint32_t), a);
+    } else {
+        a.n0 = width / 2; a.tile0 = w->peak_tile[0]; a.tile1 = w->peak_tile[1]; a.slots = w->peak_slots;
+        a.tiles0 = (a.n0 + a.tile0 - 1) / a.tile0;
+        const int tiles1 = (width - a.n0 + a.tile1 - 1) / a.tile1;
+        const dim3 grid((unsigned)(a.tiles0 + tiles1), (unsigned)height);
+        WF_LAUNCH(w, KID_WF_VIEW_PEAK, wf_view_peak, grid, 256 * sizeof(uint32_t) + (size_t)a.slots * 16, a);
+    }
+    CSDR_HIP_TRY(hipGetLastError());
+    w->view_w = width; w->view_h = height;
+    if (out_u8) {
+        CSDR_HIP_TRY(hipMemcpyAsync(out_u8, w->view.p, (size_t)(4 * pixels), hipMemcpyDeviceToHost, w->st));
+        CSDR_HIP_TRY(hipStreamSynchronize(w->st));
+    }
+    return CSDR_OK;
+}
+
+extern "C" int csdr_waterfall_device_view(csdr_waterfall *w, const uint8_t **dev, int *width, int *height) {
+    DeviceScope dev__(w ? w->ctx : nullptr);
+    if (!w || !dev) return fail(CSDR_EINVAL, "null argument");
+    if (!w->ready || w->view_w == 0) return fail(CSDR_ESTATE, "nothing rendered yet (csdr_waterfall_render_view)");
+    CSDR_HIP_TRY(hipEventRecord(w->ev_out, w->st));       // whatever the caller enqueues on the boundary stream next reads the finished view
+    CSDR_HIP_TRY(hipStreamWaitEvent(w->ctx->stream, w->ev_out, 0));
+    *dev = reinterpret_cast<const uint8_t *>(w->view.p);
+    if (width) *width = w->view_w;
+    if (height) *height = w->view_h;
     return CSDR_OK;
 }

@@ -674,6 +674,57 @@ inline bool gradient_rgba8(const float *stops, int n, uint32_t *table /*[256]*/)
     return true;
 }
 
+// ---- the waterfall's viewport (src/panel/WaterfallPanel.cpp:161-219, csdr_hip.h "Waterfall viewport") ----------------------------------------
+// The tap tables of a W x H view of the ring: which texels / scrolled rows a pixel column / row shows.  Exact integer arithmetic in int64; the
+// only floats are the blend weights, (float)((double)numerator / (double)denominator).  Independent of waterfall_ofs.
+struct ViewTap { int32_t first, count; float frac; int32_t half; };
+constexpr int kViewLinear = 0, kViewPeak = 1, kViewMaxSide = 16384;
+// pixel column px shows half 1 iff 2 px + 2 > W (the library's own definition: the reference's quads overlap by half a pixel, :185, :195, :206)
+inline bool view_columns(int fft_size, int width, int mode, ViewTap *t) {
+    if (!t || fft_size < 4 || width < 2 || width > kViewMaxSide || (mode != kViewLinear && mode != kViewPeak)) return false;
+    const int64_t half = fft_size / 2, W = width, n0 = W / 2;
+    for (int64_t px = 0; px < W; ++px) {
+        const int h = 2 * px + 2 > W ? 1 : 0;
+        ViewTap &o = t[px];
+        o.half = h;
+        if (mode == kViewLinear) {
+            // u = 1/2 + (half - 2) num / (W + 1) (:186, :192-198, :205-211 with half_texel = 1 / half, sampled at the pixel centre)
+            const int64_t num = h ? 2 * px + 2 - W : 2 * px + 1, den = 2 * (W + 1), n = (W + 1) + 2 * (half - 2) * num;
+            o.first = (int32_t)(n / den);
+            o.count = 2;
+            o.frac = (float)((double)(n % den) / (double)den);
+        } else {
+            const int64_t nh = h ? W - n0 : n0, k = h ? px - n0 : px, a = k * half / nh, b = (k + 1) * half / nh;
+            o.first = (int32_t)a;
+            o.count = (int32_t)(b > a ? b - a : 1);
+            o.frac = 0.0f;
+        }
+    }
+    return true;
+}
+inline bool view_rows(int lines, int height, int mode, ViewTap *t) {
+    if (!t || lines < 2 || lines > (1 << 20) || height < 1 || height > kViewMaxSide || (mode != kViewLinear && mode != kViewPeak)) return false;
+    const int64_t L = lines, H = height;
+    for (int64_t py = 0; py < H; ++py) {
+        ViewTap &o = t[py];
+        o.half = 0;
+        if (mode == kViewLinear) {
+            // t = (ofs + L (py + 1/2) / H) / L under GL_REPEAT, texel centres at (j + 1/2) / L: j = q + beta with n = L (2 py + 1) - H over 2 H
+            const int64_t n = L * (2 * py + 1) - H, den = 2 * H;
+            const int64_t q = n >= 0 ? n / den : -((-n + den - 1) / den);
+            o.first = (int32_t)q;
+            o.count = 2;
+            o.frac = (float)((double)(n - q * den) / (double)den);
+        } else {
+            const int64_t a = py * L / H, b = (py + 1) * L / H;
+            o.first = (int32_t)a;
+            o.count = (int32_t)(b > a ? b - a : 1);
+            o.frac = 0.0f;
+        }
+    }
+    return true;
+}
+
 // ---- block / channel sizing rules of the reference's SDR thread (SoapySDRThread.cpp:668-693) ---------------
 inline int optimal_channel_count(int64_t sample_rate) {
     if (sample_rate <= 500000) return 1;

@@ -4,11 +4,14 @@
 //   reverse the pending lines, write the runs  src/panel/WaterfallPanel.cpp:132-158    wf_update (the run table comes from the host)
 //   index -> colour through the gradient       src/panel/WaterfallPanel.cpp:26-37,     wf_rgba
 //     and the scrolled picture                 :186-213 (GL_REPEAT from waterfall_ofs)
+//   the picture scaled to a W x H viewport     src/panel/WaterfallPanel.cpp:117-120,   wf_view_linear (GL_LINEAR / GL_REPEAT, the reference's picture)
+//                                              :161-219                                wf_view_peak (the library's own: max over the footprint)
 //
 // Streaming kernels: every byte is read once and written once, so the target is the copy rate -- 16-byte accesses, no LDS beyond the 1 KB colour
 // table (wave-uniform tables live in LDS in this project), no scratch.  The pending lines and both ring textures are kept with a row pitch that is
 // a multiple of 16 bytes, so every row starts on a 16-byte boundary whatever fft_size / 2 is; a row's last fft_size / 2 % 16 bytes are written one
-// by one.  Home unit: csdr_waterfall.hip.
+// by one.  The two viewport kernels read tap tables the host designs (design.hpp: view_columns / view_rows) -- no coordinate arithmetic on the device.
+// Home unit: csdr_waterfall.hip.
 #pragma once
 #include "common.hpp"
 
@@ -183,6 +186,145 @@ CSDR_KERNEL_WF __launch_bounds__(kWfThreads) void wf_rgba(WfRgbaArgs a) {
             for (int k = 0; k < cnt; ++k) o[k] = k == 0 ? c0 : (k == 1 ? c1 : (k == 2 ? c2 : c3));
         }
     }
+}
+
+// ---- the viewport (csdr_hip.h, "Waterfall viewport"): a W x H picture of the ring from tap tables (csdr_view_tap, one per pixel column and row) ----
+struct WfViewArgs {
+    const uint8_t *ring[2];
+    const uint32_t *table;                   // 256 x RGBA8, 16-byte aligned
+    const csdr_view_tap *cols, *rows;        // [width], [height]
+    uint32_t *out;                           // [height][width] pixels, dense
+    int width, height, pitch, lines, ofs;
+    // wf_view_peak: half 0 owns pixels [0, n0) in tiles0 tiles of tile0 pixels, half 1 the rest in tiles of tile1; `slots` 16-byte LDS slots per workgroup
+    int n0, tiles0, tile0, tile1, slots;
+};
+
+// one channel-wise bilinear blend of table colours (csdr_hip.h): every operation rounded to float32 on its own, alpha 255
+__device__ __forceinline__ uint32_t wf_blend(uint32_t c00, uint32_t c10, uint32_t c01, uint32_t c11, float al, float be) {
+    uint32_t px = 0xff000000u;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float a = (float)((c00 >> (8 * ch)) & 0xffu), b = (float)((c10 >> (8 * ch)) & 0xffu);
+        const float c = (float)((c01 >> (8 * ch)) & 0xffu), d = (float)((c11 >> (8 * ch)) & 0xffu);
+        // (rounded(): hipcc's __fmul_rn / __fadd_rn are plain operators, and a product next to a sum would be contracted into one fused operation)
+        const float top = __fadd_rn(a, rounded(__fmul_rn(al, __fsub_rn(b, a))));
+        const float bot = __fadd_rn(c, rounded(__fmul_rn(al, __fsub_rn(d, c))));
+        const float m = __fadd_rn(top, rounded(__fmul_rn(be, __fsub_rn(bot, top))));
+        px |= (uint32_t)__fadd_rn(m, 0.5f) << (8 * ch);              // m lies in [0, 255]: both blends stay between their end points
+    }
+    return px;
+}
+
+// grid (groups of 4 pixels of a row / 256, image rows).  A gather: per pixel four byte reads (texels i0, i0 + 1 of ring rows j0, j1) and the blend.
+CSDR_KERNEL_WF __launch_bounds__(kWfThreads) void wf_view_linear(WfViewArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
+    if (threadIdx.x < 64) reinterpret_cast<int4 *>(tab)[threadIdx.x] = reinterpret_cast<const int4 *>(a.table)[threadIdx.x];
+    __syncthreads();
+    const int px0 = 4 * ((int)blockIdx.x * kWfThreads + (int)threadIdx.x);
+    if (px0 >= a.width) return;
+    const int cnt = min(4, a.width - px0);
+    int64_t at[4];                                                    // byte offset of texel i0 inside a ring row, in the pixel's half
+    const uint8_t *tex[4];
+    float al[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const csdr_view_tap t = a.cols[min(px0 + k, a.width - 1)];
+        tex[k] = t.half ? a.ring[1] : a.ring[0];
+        at[k] = t.first;
+        al[k] = t.frac;
+    }
+    for (int py = (int)blockIdx.y; py < a.height; py += (int)gridDim.y) {
+        const csdr_view_tap rt = a.rows[py];
+        const int j0 = (int)(((int64_t)a.ofs + rt.first + a.lines) % a.lines), j1 = j0 + 1 == a.lines ? 0 : j0 + 1;       // GL_REPEAT
+        uint32_t c[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint8_t *r0 = tex[k] + (int64_t)j0 * a.pitch + at[k], *r1 = tex[k] + (int64_t)j1 * a.pitch + at[k];
+            c[k] = wf_blend(tab[r0[0]], tab[r0[1]], tab[r1[0]], tab[r1[1]], al[k], rt.frac);
+        }
+        const int64_t base = (int64_t)py * a.width + px0;
+        uint32_t *o = a.out + base;
+        if (cnt == 4 && (base & 3) == 0) *reinterpret_cast<int4 *>(o) = make_int4((int)c[0], (int)c[1], (int)c[2], (int)c[3]);
+        else {
+#pragma unroll 1
+            for (int k = 0; k < cnt; ++k) o[k] = k == 0 ? c[0] : (k == 1 ? c[1] : (k == 2 ? c[2] : c[3]));        // (a loop that stays a loop, as in wf_rgba)
+        }
+    }
+}
+
+// byte-wise unsigned max of two words in plain integer arithmetic.  Bit 7 of each byte of d says whether the low 7 bits of x reach those of y (no
+// borrow crosses a byte: 128 + xl - yl lies in [1, 255]); the top bits decide first.
+__device__ __forceinline__ unsigned wf_max_u8x4(unsigned x, unsigned y) {
+    const unsigned d = (x | 0x80808080u) - (y & 0x7f7f7f7fu);
+    const unsigned ge = ((x & ~y) | (~(x ^ y) & d)) & 0x80808080u;
+    const unsigned m = (ge >> 7) * 0xffu;                            // 0xff in every byte where x >= y
+    return (x & m) | (y & ~m);
+}
+__device__ __forceinline__ int4 wf_max_u8x16(int4 x, int4 y) {
+    return make_int4((int)wf_max_u8x4((unsigned)x.x, (unsigned)y.x), (int)wf_max_u8x4((unsigned)x.y, (unsigned)y.y),
+                     (int)wf_max_u8x4((unsigned)x.z, (unsigned)y.z), (int)wf_max_u8x4((unsigned)x.w, (unsigned)y.w));
+}
+// the mask that keeps bytes [lo, hi) of a word (any lo, hi: clamped to 0 .. 4)
+__device__ __forceinline__ unsigned wf_keep_bytes(int lo, int hi) {
+    const unsigned below_hi = hi >= 4 ? 0xffffffffu : (hi <= 0 ? 0u : (1u << (8 * hi)) - 1u);
+    const unsigned below_lo = lo >= 4 ? 0xffffffffu : (lo <= 0 ? 0u : (1u << (8 * lo)) - 1u);
+    return below_hi & ~below_lo;
+}
+__device__ __forceinline__ int4 wf_keep_bytes16(int4 v, int lo, int hi) {
+    return make_int4((int)((unsigned)v.x & wf_keep_bytes(lo, hi)), (int)((unsigned)v.y & wf_keep_bytes(lo - 4, hi - 4)),
+                     (int)((unsigned)v.z & wf_keep_bytes(lo - 8, hi - 8)), (int)((unsigned)v.w & wf_keep_bytes(lo - 12, hi - 12)));
+}
+
+// grid (tiles of both halves, image rows).  A workgroup owns up to 256 consecutive pixels of one half in one image row; tiles end on footprint
+// boundaries, so no footprint straddles two of them.  Pass 1: the element-wise max of the footprint's ring rows over the tile's texel span, in
+// 16-byte loads (rows have a 16-byte pitch), into LDS; the bytes outside the span are cleared.  One barrier.  Pass 2: each work-item scans its pixel's
+// bytes in LDS word by word and looks the colour of the largest up.  The max is separable, so every texel is read once.  A single pixel whose
+// span does not fit the slots (the host then makes the tile that one pixel) is folded: slot s holds the max of chunks s, s + slots, ...
+CSDR_KERNEL_WF __launch_bounds__(kWfThreads) void wf_view_peak(WfViewArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
+    int4 *span = reinterpret_cast<int4 *>(smem + 256 * sizeof(uint32_t));
+    const int tid = (int)threadIdx.x;
+    if (tid < 64) reinterpret_cast<int4 *>(tab)[tid] = reinterpret_cast<const int4 *>(a.table)[tid];
+    const int h = (int)blockIdx.x >= a.tiles0 ? 1 : 0;
+    const int per = h ? a.tile1 : a.tile0, nh = h ? a.width - a.n0 : a.n0;
+    const int k0 = (h ? (int)blockIdx.x - a.tiles0 : (int)blockIdx.x) * per;
+    const int kn = min(per, nh - k0);                                 // pixels of this tile (>= 1)
+    const csdr_view_tap *cols = a.cols + (h ? a.n0 : 0) + k0;
+    const csdr_view_tap rt = a.rows[blockIdx.y];
+    const int t0 = cols[0].first, t1 = cols[kn - 1].first + cols[kn - 1].count;         // the tile's texel span [t0, t1)
+    const int c0 = t0 >> 4, nchunks = ((t1 + 15) >> 4) - c0;
+    const bool fold = nchunks > a.slots;
+    const int nslots = fold ? a.slots : nchunks;
+    const uint8_t *ring = (h ? a.ring[1] : a.ring[0]) + 16 * (int64_t)c0;
+    const int row0 = (int)(((int64_t)a.ofs + rt.first) % a.lines);    // scrolled row r is ring row (ofs + r) mod lines
+    for (int s = tid; s < nslots; s += kWfThreads) {
+        int4 acc = make_int4(0, 0, 0, 0);
+        for (int cc = s; cc < nchunks; cc += a.slots) {               // (a second turn only when folded)
+            int rr = row0;
+            int4 m = *reinterpret_cast<const int4 *>(ring + (int64_t)rr * a.pitch + 16 * (int64_t)cc);
+            for (int r = 1; r < rt.count; ++r) {
+                if (++rr == a.lines) rr = 0;
+                m = wf_max_u8x16(m, *reinterpret_cast<const int4 *>(ring + (int64_t)rr * a.pitch + 16 * (int64_t)cc));
+            }
+            if (cc == 0) m = wf_keep_bytes16(m, t0 - 16 * c0, 16);
+            if (cc == nchunks - 1) m = wf_keep_bytes16(m, 0, t1 - 16 * (c0 + cc));
+            acc = wf_max_u8x16(acc, m);
+        }
+        span[s] = acc;
+    }
+    __syncthreads();
+    if (tid >= kn) return;
+    const csdr_view_tap t = cols[tid];
+    const int s = fold ? 0 : t.first - 16 * c0, e = fold ? 16 * nslots : s + t.count;   // this pixel's bytes in LDS
+    const unsigned *words = reinterpret_cast<const unsigned *>(span);
+    unsigned best = 0;
+    for (int w = s >> 2; 4 * w < e; ++w) {
+        const unsigned x = words[w] & wf_keep_bytes(s - 4 * w, e - 4 * w);
+        best = max(best, max(max(x & 0xffu, (x >> 8) & 0xffu), max((x >> 16) & 0xffu, x >> 24)));
+    }
+    a.out[(int64_t)blockIdx.y * a.width + (h ? a.n0 : 0) + k0 + tid] = tab[best];
 }
 
 }  // namespace csdr

@@ -498,6 +498,28 @@ def design_gradient(stops, length=256):
     return r, g, b
 
 
+VIEW_MODES = {"linear": H.WF_VIEW_LINEAR, "peak": H.WF_VIEW_PEAK}
+VIEW_TAP = np.dtype([("first", np.int32), ("count", np.int32), ("frac", np.float32), ("half", np.int32)])
+
+
+def _view_mode(mode):
+    return VIEW_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def design_view_columns(fft_size, width, mode="linear"):
+    """the column taps of a `width` pixel wide view of a waterfall of fft_size points (host only) -> structured array [width] of VIEW_TAP"""
+    t = np.zeros(max(int(width), 0), VIEW_TAP)
+    H.check(H.lib().csdr_design_view_columns(int(fft_size), int(width), _view_mode(mode), t.ctypes.data_as(C.c_void_p)))
+    return t
+
+
+def design_view_rows(lines, height, mode="linear"):
+    """the row taps of a `height` pixel high view of a ring of `lines` lines (host only) -> structured array [height] of VIEW_TAP"""
+    t = np.zeros(max(int(height), 0), VIEW_TAP)
+    H.check(H.lib().csdr_design_view_rows(int(lines), int(height), _view_mode(mode), t.ctypes.data_as(C.c_void_p)))
+    return t
+
+
 class Waterfall:
     """WaterfallPanel's arithmetic (csdr_waterfall): spectrum lines quantised to bytes, two ring textures, the themed RGBA picture."""
 
@@ -568,6 +590,22 @@ class Waterfall:
         p = C.c_void_p()
         H.check(self._l.csdr_waterfall_device_rgba(self.h, C.byref(p)))
         return p.value
+
+    def view(self, width, height, mode="linear", fetch=True):
+        """the ring scaled to a viewport, [height, width, 4] uint8: mode "linear" is the reference's GL_LINEAR picture, "peak" the maximum over
+        every pixel's footprint; fetch=False renders it and leaves it on the device (device_view)"""
+        if not fetch:
+            H.check(self._l.csdr_waterfall_render_view(self.h, int(width), int(height), _view_mode(mode), None, 0))
+            return None
+        out = np.empty((max(int(height), 0), max(int(width), 0), 4), np.uint8)
+        H.check(self._l.csdr_waterfall_render_view(self.h, int(width), int(height), _view_mode(mode), out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def device_view(self):
+        """(device pointer, width, height) of the last rendered view; the context's boundary stream waits for it"""
+        p, w, h = C.c_void_p(), C.c_int(), C.c_int()
+        H.check(self._l.csdr_waterfall_device_view(self.h, C.byref(p), C.byref(w), C.byref(h)))
+        return p.value, w.value, h.value
 
     def close(self):
         if self.h:

@@ -74,6 +74,13 @@ class DistribState(C.Structure):
                 ("dropped", C.c_int64), ("n_lines", C.c_int32), ("line_len", C.c_int32)]
 
 
+class ViewTap(C.Structure):
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("frac", C.c_float), ("half", C.c_int32)]
+
+
+WF_VIEW_LINEAR, WF_VIEW_PEAK = 0, 1
+
+
 class P2pOp(C.Structure):
     _fields_ = [("peer", C.c_int32), ("recv", C.c_int32), ("buf", C.c_void_p), ("n_samples", C.c_int64)]
 
@@ -241,6 +248,10 @@ ABI = {
     "csdr_waterfall_fetch_index": (_i, [_p, _i, _p, _i64]),
     "csdr_waterfall_fetch_rgba": (_i, [_p, _i, _i, _p, _i64]),
     "csdr_waterfall_device_rgba": (_i, [_p, _pp]),
+    "csdr_design_view_columns": (_i, [_i, _i, _i, _p]),
+    "csdr_design_view_rows": (_i, [_i, _i, _i, _p]),
+    "csdr_waterfall_render_view": (_i, [_p, _i, _i, _i, _p, _i64]),
+    "csdr_waterfall_device_view": (_i, [_p, _pp, C.POINTER(_i), C.POINTER(_i)]),
     "csdr_distrib_create": (_i, [_p, _i, _pp]),
     "csdr_distrib_destroy": (None, [_p]),
     "csdr_distrib_set_fft_size": (_i, [_p, _i]),

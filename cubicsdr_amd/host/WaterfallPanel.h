@@ -4,7 +4,8 @@
 // With a context the panel is a csdr_waterfall: lines are quantised, kept in the two ring textures and coloured in HBM (include/csdr_hip.h,
 // "WaterfallPanel"), and stepFrom() takes a line straight from a SpectrumVisualProcessor's point buffer without a trip over the link.  Without a
 // context (ctx == nullptr) the same arithmetic runs on the host, spelled out below as the reference spells it -- for a build without a device and
-// as the yardstick of the tests; both give the same bytes.  Scaling the picture to a viewport stays with the GUI.
+// as the yardstick of the tests; both give the same bytes.  renderView() is the picture scaled to a viewport (csdr_hip.h, "Waterfall viewport"):
+// what drawPanelContents draws through GL, as bytes a headless consumer can use.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -140,6 +141,49 @@ public:
                 for (size_t i = 0; i < half; ++i)
                     std::memcpy(&out[(((size_t)r * 2 + j) * half + i) * 4], &table_[4 * waterfall[j][row * half + i]], 4);
         }
+        return true;
+    }
+
+    // the ring scaled to width x height pixels of RGBA8 (:161-219 into a viewport): mode CSDR_WF_VIEW_LINEAR is the reference's GL_LINEAR / GL_REPEAT
+    // picture, CSDR_WF_VIEW_PEAK the maximum index over each pixel's footprint (csdr_hip.h, "Waterfall viewport", items 2-4).  The taps are the
+    // library's host-only design functions in both cases.
+    bool renderView(int width, int height, int mode, std::vector<unsigned char> &out) {
+        const size_t W = width > 0 ? (size_t)width : 0, Hh = height > 0 ? (size_t)height : 0;
+        if (wf_) {
+            out.resize(W * Hh * 4);
+            return errlog.ok(csdr_waterfall_render_view(wf_, width, height, mode, out.data(), (int64_t)out.size()), "csdr_waterfall_render_view");
+        }
+        if (!texInitialized) return false;
+        std::vector<csdr_view_tap> ct(W), rt(Hh);
+        if (!errlog.ok(csdr_design_view_columns((int)fft_size, width, mode, ct.data()), "csdr_design_view_columns")) return false;
+        if (!errlog.ok(csdr_design_view_rows(waterfall_lines, height, mode, rt.data()), "csdr_design_view_rows")) return false;
+        const size_t half = fft_size / 2;
+        const int L = waterfall_lines, ofs = waterfall_ofs[0];
+        out.resize(W * Hh * 4);
+        for (size_t py = 0; py < Hh; ++py)
+            for (size_t px = 0; px < W; ++px) {
+                const std::vector<unsigned char> &tex = waterfall[ct[px].half];
+                unsigned char *o = &out[(py * W + px) * 4];
+                if (mode == CSDR_WF_VIEW_PEAK) {
+                    unsigned char best = 0;
+                    for (int r = rt[py].first; r < rt[py].first + rt[py].count; ++r) {
+                        const unsigned char *row = &tex[(size_t)((ofs + r) % L) * half];
+                        for (int i = ct[px].first; i < ct[px].first + ct[px].count; ++i) if (row[i] > best) best = row[i];
+                    }
+                    std::memcpy(o, &table_[4 * best], 4);
+                    continue;
+                }
+                const size_t j0 = (size_t)((ofs + rt[py].first + L) % L), j1 = (j0 + 1) % (size_t)L, i0 = (size_t)ct[px].first;
+                const unsigned char *c00 = &table_[4 * tex[j0 * half + i0]], *c10 = &table_[4 * tex[j0 * half + i0 + 1]];
+                const unsigned char *c01 = &table_[4 * tex[j1 * half + i0]], *c11 = &table_[4 * tex[j1 * half + i0 + 1]];
+                auto lerp = [](float a, float b, float w) { volatile float d = b - a; volatile float m = w * d; volatile float r = a + m; return (float)r; };      // (volatile: each step stored as a float)
+                for (int ch = 0; ch < 3; ++ch) {
+                    const float top = lerp((float)c00[ch], (float)c10[ch], ct[px].frac), bot = lerp((float)c01[ch], (float)c11[ch], ct[px].frac);
+                    volatile float m = lerp(top, bot, rt[py].frac);
+                    o[ch] = (unsigned char)(m + 0.5f);
+                }
+                o[3] = 255;
+            }
         return true;
     }
 

@@ -471,7 +471,8 @@ int  csdr_bank_scope_frame(csdr_bank *bank, int slot, csdr_scope_frame *out);
 /* ------------------------------------------------------------------ WaterfallPanel (src/panel/WaterfallPanel.cpp, src/util/Gradient.cpp)
  * replaces: setup :13-24, setPoints :39-49, step :51-83, update :85-159, refreshTheme :26-37 with Gradient::generate (Gradient.cpp:37-85), and
  * the unscaled picture of drawPanelContents :161-219; fed as WaterfallCanvas::processInputQueue feeds it (src/visual/WaterfallCanvas.cpp:89-126).
- * The display points of a spectrum stay in HBM from csdr_spec_process to the coloured picture; scaling and filtering to a viewport stay with the GUI.
+ * The display points of a spectrum stay in HBM from csdr_spec_process to the coloured picture, and to the picture scaled and filtered to a viewport
+ * ("Waterfall viewport" below).
  * All work of a waterfall runs on a stream of its own; the calls that return data to the host synchronise it.
  *
  * 1. Quantiser (:64-72).  wv = v < 0 ? 0 : (v > 0.99 ? 0.99 : v), stored to a float, then (unsigned char)floor(wv * 255.0).  The comparison with
@@ -526,6 +527,57 @@ int  csdr_waterfall_offset(const csdr_waterfall *wf, int half);                 
 int  csdr_waterfall_fetch_index(csdr_waterfall *wf, int half, uint8_t *out_u8, int64_t cap);
 int  csdr_waterfall_fetch_rgba(csdr_waterfall *wf, int first_row, int n_rows, uint8_t *out_u8, int64_t cap);
 int  csdr_waterfall_device_rgba(csdr_waterfall *wf, const uint8_t **dev);
+
+/* ------------------------------------------------------------------ Waterfall viewport (src/panel/WaterfallPanel.cpp:161-219)
+ * replaces: the two textured quads drawPanelContents draws with GL_LINEAR / GL_REPEAT (:117-120) into whatever viewport the canvas has -- a
+ * width x height RGBA8 picture of the ring, rendered in HBM from the two ring textures and the colour table, so that a headless consumer pulls
+ * W * H * 4 bytes over the link and not the ring at texture resolution.  half = fft_size / 2, L = lines, ofs = waterfall_ofs; image row 0 is the
+ * top, as in fetch_rgba.  All coordinate arithmetic is exact integer arithmetic on the host (int64); the device reads tables of csdr_view_tap.
+ *
+ * 1. Limits.  fft_size >= 4, 2 <= width <= 16384, 1 <= height <= 16384, mode one of the two below; anything else is CSDR_EINVAL.  Before the
+ *    textures exist the call returns what csdr_waterfall_fetch_rgba returns then (CSDR_ESTATE); a host buffer that is too small is CSDR_ERANGE.
+ *    A refusal renders nothing and changes nothing.
+ * 2. Which half a pixel shows.  The reference's quads meet with a half-pixel overlap (:185, :195, :206) and the second is drawn over the first; GL
+ *    leaves a pixel centre that lies exactly on an edge to the implementation.  THE LIBRARY'S OWN DEFINITION: pixel column px shows half 1 iff
+ *    2 px + 2 > W, otherwise half 0 -- W / 2 pixels each for an even W, the middle pixel to half 1 for an odd one.
+ * 3. CSDR_WF_VIEW_LINEAR is the reference's picture: the texture coordinates are affine over each quad and sampled at pixel centres.
+ *    Columns: num = 2 px + 1 (half 0) or 2 px + 2 - W (half 1); u = 0.5 + (half - 2) num / (W + 1), which is :186, :192-198 and :205-211 with
+ *    half_texel = 1 / half -- the reference's bias trims one texel at each end of a half, and that is kept.  i0 = floor(u), i1 = i0 + 1,
+ *    alpha = u - i0; i0 lies in [0, half - 2], so GL_REPEAT never acts horizontally.
+ *    Rows: n = L (2 py + 1) - H, q = floor(n / 2H) in [-1, L - 1], beta = (n mod 2H) / 2H; ring rows j0 = (ofs + q + L) mod L and
+ *    j1 = (j0 + 1) mod L.  Under GL_REPEAT with H > L the top and bottom pixel rows blend the newest line with the oldest: the reference's
+ *    behaviour, kept.  With H = L every beta is 0 and row py is ring row (ofs + py) mod L, as in fetch_rgba.
+ *    alpha and beta are (float)((double)numerator / (double)denominator) of those integers.
+ *    The texture holds colours, not indices (:122, GL_RGB from GL_COLOR_INDEX), so table colours are blended, per channel, from the table's bytes
+ *    taken as floats: top = c00 + alpha (c10 - c00), bot = c01 + alpha (c11 - c01), m = top + beta (bot - top), channel = (uint8)(m + 0.5f),
+ *    every operation rounded to float32 on its own; alpha channel 255.  (cXY: texel iX of ring row jY.)  GL's filter precision is
+ *    implementation-defined: this is THE LIBRARY'S OWN DEFINITION, in the sense of item 5 of the block above.
+ * 4. CSDR_WF_VIEW_PEAK is THE LIBRARY'S OWN MODE, not the reference's: GL_LINEAR without mipmaps samples 2 x 2 texels per pixel, which at 34
+ *    points per pixel skips 94 % of the bins.  Here no bin and no line is lost.  Half h owns n_h pixels by item 2; its k-th pixel shows texels
+ *    [k half div n_h, (k + 1) half div n_h), image row py shows scrolled rows [py L div H, (py + 1) L div H), an empty range becomes its single
+ *    first element; scrolled row r is ring row (ofs + r) mod L.  The pixel is the table colour of the MAXIMUM INDEX BYTE over that rectangle.
+ *    With W = 2 half and H = L the picture equals csdr_waterfall_fetch_rgba(0, L) byte for byte; with n_h <= half and H <= L every texel of the
+ *    ring is read exactly once.
+ * 5. Tap tables.  csdr_design_view_columns / csdr_design_view_rows are that arithmetic (host only, no device needed): LINEAR gives first = i0 or
+ *    q, count = 2, frac = alpha or beta; PEAK gives the range's start and length and frac = 0; `half` is the column's half (0 for rows).  They
+ *    do not depend on ofs: a waterfall keeps its tables on the device per (fft_size, lines, width, height, mode) and rebuilds them only when one
+ *    of those changes.
+ * 6. render_view renders on the waterfall's stream into a buffer of its own ([height][width] RGBA8, dense): what csdr_waterfall_device_rgba promises
+ *    about the last fetch_rgba picture still holds.  out_u8 == NULL leaves the picture on the device; otherwise width * height * 4 bytes are copied
+ *    to the host and the stream is synchronised.  csdr_waterfall_device_view returns the last rendered view and its size and makes the context's
+ *    boundary stream wait for it; it stays valid until the next render_view or setup. */
+#define CSDR_WF_VIEW_LINEAR 0
+#define CSDR_WF_VIEW_PEAK   1
+typedef struct csdr_view_tap {
+    int32_t first, count;      /* LINEAR: i0 or q, 2; PEAK: start and length of the range */
+    float   frac;              /* LINEAR: alpha or beta; PEAK: 0 */
+    int32_t half;              /* columns: the half the pixel shows; rows: 0 */
+} csdr_view_tap;
+CSDR_STATIC_ASSERT(sizeof(csdr_view_tap) == 16 && offsetof(csdr_view_tap, frac) == 8 && offsetof(csdr_view_tap, half) == 12, "csdr_view_tap layout");
+int  csdr_design_view_columns(int fft_size, int width, int mode, csdr_view_tap *taps);       /* taps[width] */
+int  csdr_design_view_rows(int lines, int height, int mode, csdr_view_tap *taps);            /* taps[height]; lines 2 .. 2^20 */
+int  csdr_waterfall_render_view(csdr_waterfall *wf, int width, int height, int mode, uint8_t *out_u8, int64_t cap);
+int  csdr_waterfall_device_view(csdr_waterfall *wf, const uint8_t **dev, int *width, int *height);
 
 /* ------------------------------------------------------------------ FFTDataDistributor (src/process/FFTDataDistributor.cpp)
  * replaces: the ctor's defaults :11, setFFTSize :15-18, setLinesPerSecond :20-22 and, per csdr_distrib_push, ONE popped input of process() :41-143
