@@ -27,6 +27,8 @@ unsigned long long csdr_design_resamp_count(unsigned long long K, unsigned phase
 unsigned csdr_design_nco_word(float theta) { return nco_phase_word(theta); }
 void csdr_design_sine_table(float *t) { auto v = nco_sine_table(); std::memcpy(t, v.data(), 1024 * sizeof(float)); }
 void csdr_design_channelizer(unsigned M, unsigned m, float as, float *taps) { auto v = channelizer_taps(M, m, as); std::memcpy(taps, v.data(), v.size() * sizeof(float)); }
+// the oversampled bank's prototype (firpfbch2), in the same commutator form: taps[M][2 m]
+void csdr_design_channelizer2(unsigned M, unsigned m, float as, float *taps) { auto v = channelizer2_taps(M, m, as); std::memcpy(taps, v.data(), v.size() * sizeof(float)); }
 void csdr_design_dc_notch(unsigned m, float as, float *h) { auto v = dc_notch_taps(m, as); std::memcpy(h, v.data(), v.size() * sizeof(float)); }
 int csdr_design_butter_sos(unsigned order, float fc, float *b, float *a) {
     auto v = butter_lowpass_sos(order, fc);

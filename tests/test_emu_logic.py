@@ -15,6 +15,7 @@ import pytest
 
 import tests.test_gpu_fft_exact as X
 import tests.test_gpu_parity as G
+import tests.test_gpu_sample_path_exact as S
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "emu"))
@@ -316,3 +317,18 @@ def test_emu_spectrum_display_points_against_float64(ctx, F):
     """contiguous frames over three calls (frame 0 of a call split by the carry at an odd offset), the fused 2^17 chain included: display points
     within the transform bound carried through the display arithmetic"""
     X.check_display_exact(ctx, F)
+
+
+@pytest.mark.parametrize("case,signal", [pytest.param(c, s, marks=() if (c, s) in S.FE_QUICK else full) for c, s in S.FE_RUNS])
+def test_emu_frontend_against_float64(ctx, case, signal):
+    """every front-end kernel against the float64 cascade of the channel row it read, output by output (tests/test_gpu_sample_path_exact.py): a wrong
+    tap, table entry or window index fails here without a GPU; one case per kernel by default, both inputs of every case in the full suite"""
+    S.check_frontend(ctx, case, signal, liquid=False, quiet=True)
+
+
+@pytest.mark.parametrize("M,frames,os2", [pytest.param(M, fr, o, marks=() if (M, o) in S.CH_QUICK else full)
+                                          for o, sizes in ((False, S.CRITICAL), (True, S.OVERSAMPLED)) for M, fr in sizes])
+def test_emu_channelizer_against_float64(ctx, M, frames, os2):
+    """every row of every frame of both banks against the float64 polyphase filter and transform; M = 10, 20, 122, 116 (vector and matrix-pipe forms of
+    chan_analyze_p2, the FFT kernel, its prime pass) and the oversampled 38 and 40 by default"""
+    S.check_channelizer(ctx, M, frames, oversampled=os2, liquid=False, quiet=True)

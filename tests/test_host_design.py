@@ -159,6 +159,26 @@ def test_channelizer_taps(D, O, M):
     assert rel_err(got.reshape(-1).astype(np.complex64), y) < 5e-6
 
 
+@pytest.mark.parametrize("M", [4, 6, 20, 122, 200])
+def test_channelizer2_taps(D, O, M):
+    """csdr_design_channelizer2 (the oversampled bank's prototype as uploaded) and the float64 restatement built on it
+    (tests/sample_path_oracle.py: firpfbch) against the oracle's firpfbch2: M / 2 new samples per frame, M / 2 odd included"""
+    from tests.sample_path_oracle import firpfbch
+    rng = np.random.default_rng(M)
+    nf = 41
+    x = ((rng.standard_normal(M // 2 * nf) + 1j * rng.standard_normal(M // 2 * nf)) * 0.3).astype(np.complex64)
+    q = O.firpfbch2_crcf_create_kaiser(A.LIQUID_ANALYZER, M, 4, 60.0); y = np.zeros(M * nf, np.complex64)
+    O.oracle_firpfbch2_block(C.c_void_p(q), M, A.ptr(x), nf, A.ptr(y))
+    got, _, _ = firpfbch(x, M, oversampled=True)
+    assert rel_err(got.reshape(-1).astype(np.complex64), y) < 5e-6
+    # ... and the critically sampled form of the same restatement, against firpfbch
+    x = x[:M * (nf // 2)]
+    q = O.firpfbch_crcf_create_kaiser(A.LIQUID_ANALYZER, M, 4, 60.0); y = np.zeros_like(x)
+    O.oracle_firpfbch_analyzer_block(C.c_void_p(q), M, A.ptr(x), nf // 2, A.ptr(y))
+    got, _, _ = firpfbch(x, M)
+    assert rel_err(got.reshape(-1).astype(np.complex64), y) < 5e-6
+
+
 def test_modem_filter_designs(D, O):
     h = np.zeros(51, np.float32); D.csdr_design_dc_notch(25, C.c_float(30.0), A.ptr(h))
     w = np.zeros(51, np.float32); O.liquid_firdes_notch(25, 0.0, 30.0, A.ptr(w))
