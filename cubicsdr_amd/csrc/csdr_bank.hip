@@ -97,7 +97,10 @@ extern "C" void csdr_bank_destroy(csdr_bank *b) {
         if (b->ev_fe_done[k]) (void)hipEventDestroy(b->ev_fe_done[k]);
         if (b->ev_audio_done[k]) (void)hipEventDestroy(b->ev_audio_done[k]);
         if (b->ev_tables_read[k]) (void)hipEventDestroy(b->ev_tables_read[k]);
+        if (b->iq_read_pending[k]) (void)hipEventSynchronize(b->ev_iq_read[k]);      // (a reader on a stream that is not the context's)
+        if (b->ev_iq_read[k]) (void)hipEventDestroy(b->ev_iq_read[k]);
     }
+    if (b->ev_iq_ready) (void)hipEventDestroy(b->ev_iq_ready);
     for (auto &s : b->slots) if (s.slab) (void)hipFree(s.slab);
     b->cfgs.release(); b->tables.release(); b->arms.release(); b->mconsts.release();
     for (int r = 0; r < kStageRing; ++r) {
@@ -524,6 +527,10 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
     // BEFORE the lane waits for the channelizer (on separate streams the fetch runs beside it), the front-end kernels behind that wait
     const int pk = post->cur;
     if (b->audio_pending[bpar]) if (int rc = c->wait(b->ev_audio_done[bpar], LANE_AUDIO, LANE_FE)) return rc;
+    if (b->iq_read_pending[bpar]) {          // a device-side reader of this parity's resampled IQ (bank_iq_release): the front-end rewrites it behind that reader
+        CSDR_HIP_TRY(hipStreamWaitEvent(st, b->ev_iq_read[bpar], 0));
+        b->iq_read_pending[bpar] = false;
+    }
     // Where the channelizer has a stream of its own, the fetch rides on THAT stream, behind the channelizer of this batch: a one-block call is bound by
     // the chain of the demodulators' stream (tables 4 + front-end 19 + modem / audio 22 us and three gaps), the channelizer's stream has
     // half of that; the front-end's wait for the channelizer becomes its wait for the fetch (one event either way).
@@ -706,6 +713,25 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
     if (fetch_on_post) { CSDR_HIP_TRY(hipEventRecord(b->ev_tables_read[bpar], st_a)); b->tables_read_pending[bpar] = true; }      // the last reader of this parity's device tables
     (void)st_a;
     b->seq++;
+    return CSDR_OK;
+}
+
+// ---- the resampled IQ of the last execute for a reader that stays on the device (csdr_objects.hpp) ----
+int bank_iq_acquire(csdr_bank *b, hipStream_t reader) {
+    if (!b || b->last_nb == 0) return fail(CSDR_ESTATE, "no csdr_bank_execute yet");
+    if (!b->ev_iq_ready) {
+        CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_iq_ready, hipEventDisableTiming));
+        for (int k = 0; k < 2; ++k) CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_iq_read[k], hipEventDisableTiming));
+    }
+    CSDR_HIP_TRY(hipEventRecord(b->ev_iq_ready, b->ctx->lanes[LANE_FE]));
+    CSDR_HIP_TRY(hipStreamWaitEvent(reader, b->ev_iq_ready, 0));
+    return CSDR_OK;
+}
+int bank_iq_release(csdr_bank *b, hipStream_t reader) {
+    if (b->seq == 0) return CSDR_OK;         // no batch has run a slot: nothing was read
+    const int par = (int)((b->seq - 1) & 1); // the batch that was read; a slot's buffer of that batch is rewritten two of the slot's batches later at the earliest
+    CSDR_HIP_TRY(hipEventRecord(b->ev_iq_read[par], reader));
+    b->iq_read_pending[par] = true;
     return CSDR_OK;
 }
 

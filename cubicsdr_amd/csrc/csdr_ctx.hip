@@ -145,7 +145,8 @@ static const char *kKernelNames[KID_COUNT] = {
     "spec_fft_radix", "spec_fft_rows", "spec_average", "spec_extrema", "spec_display", "spec_misc",
     "digital_demod",
     "wf_quantize", "wf_update", "wf_rgba", "wf_view_linear", "wf_view_peak",
-    "distrib_gather"};
+    "distrib_gather",
+    "specbank_process"};
 static int prof_drain(csdr_ctx *c) {
     if (int rc = c->sync_all()) return rc;
     std::lock_guard<std::mutex> lk(c->prof_mu);

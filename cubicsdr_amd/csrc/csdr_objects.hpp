@@ -133,6 +133,10 @@ struct csdr_bank {
     std::vector<GmskJob> gmsk_jobs_h;
     DevBuf<TableJob> tab_jobs;               // the table slots' launch records
     std::vector<TableJob> tab_jobs_h;
+    // a reader of the slots' resampled IQ that stays on the device (bank_iq_acquire / _release: the spectrum bank on its own stream); by parity of the
+    // batch it read.  Created at the first acquire: a bank nobody reads this way never has them
+    hipEvent_t ev_iq_ready = nullptr, ev_iq_read[2] = {nullptr, nullptr};
+    bool iq_read_pending[2] = {false, false};    // ev_iq_read[k] is recorded and not yet waited for
 };
 
 // =================================================================================================== spectrum points for device-side readers
@@ -148,6 +152,15 @@ struct SpecPointsRef {
 int spec_points_acquire(csdr_spec *s, hipStream_t reader, SpecPointsRef *out);
 int spec_points_release(csdr_spec *s, hipStream_t reader);
 csdr_ctx *spec_ctx(const csdr_spec *s);      // the context a spectrum was created on (csdr_spec_process_distrib checks it against the distributor's)
+
+// =================================================================================================== resampled IQ for device-side readers
+// The bank-side counterpart of the above: the slots' resampled IQ of the last execute (where csdr_bank_fetch_iq reads it), for a reader that stays in
+// HBM (csdr_specbank_process_bank).  `reader` is made to wait for the front-end of that execute by an event (no host synchronisation); after enqueueing
+// its reads the reader calls bank_iq_release, and the execute that rewrites that parity's buffers -- the second one after -- waits for them.  (csdr_bank.hip)
+int bank_iq_acquire(csdr_bank *b, hipStream_t reader);
+int bank_iq_release(csdr_bank *b, hipStream_t reader);
+// block bb of a slot's last execute inside that buffer: the samples in front of it are the earlier blocks' (BlockPlan::j0, batch-relative from 0)
+static inline const float2 *bank_slot_iq(const SlotHost &s) { return s.cfg.iq + (size_t)s.last_parity * ((size_t)kIqHist + s.cfg.cap_iq) + kIqHist; }
 
 // internal modem id: NCO + msresamp only, no modem / audio stage (the zoomed spectrum view's shift + resample, SpectrumVisualProcessor.cpp:306-379)
 #define CSDR_MODEM_FRONTEND_ONLY 100

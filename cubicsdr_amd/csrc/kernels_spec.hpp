@@ -156,7 +156,8 @@ __device__ inline void fft4096_regs(float2 (&v)[16], float2 *lds, const float2 *
     dft_reg<16>(v);
 }
 
-// ---- In-LDS Stockham autosort FFT of one sequence of length L <= 2048 (generic small sizes) ---------------------
+// ---- In-LDS Stockham autosort FFT of one sequence of length L <= 4096 = kFftMaxLds (generic small sizes; the main spectrum uses it up to 2048,
+// the audio scope and the spectrum bank up to 4096: two arrays of L float2, 64 KB at the limit) -------------------
 __device__ inline float2 *lds_fft(float2 *a, float2 *b, int L, const float2 *__restrict__ tw4096) {
     const int tid = threadIdx.x;
     int Ns = 1;

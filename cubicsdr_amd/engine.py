@@ -489,6 +489,87 @@ class SpectrumProcessor:
             self.h = C.c_void_p()
 
 
+class SpectrumBank:
+    """N independent SpectrumVisualProcessors of one fft_size (csdr_specbank): one per demodulator, all slots and all inputs of a call in one launch;
+    state and points stay in HBM."""
+
+    def __init__(self, ctx, fft_size, max_slots, max_frames=1):
+        self._l = H.lib()
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        H.check(self._l.csdr_specbank_create(ctx.h, C.byref(self.h)))
+        self.setup(fft_size, max_slots, max_frames)
+
+    def setup(self, fft_size, max_slots, max_frames=1):
+        H.check(self._l.csdr_specbank_setup(self.h, int(fft_size), int(max_slots), int(max_frames)))
+        self.fft_size, self.max_slots, self.max_frames = int(fft_size), int(max_slots), int(max_frames)
+
+    def set_average_rate(self, r):
+        H.check(self._l.csdr_specbank_set_average_rate(self.h, float(r)))
+
+    def set_scale_factor(self, f):
+        H.check(self._l.csdr_specbank_set_scale_factor(self.h, float(f)))
+
+    def set_peak_hold(self, enabled):
+        H.check(self._l.csdr_specbank_set_peak_hold(self.h, int(bool(enabled))))
+
+    def get_peak_hold(self):
+        return bool(self._l.csdr_specbank_get_peak_hold(self.h))
+
+    def reset_slot(self, slot):
+        H.check(self._l.csdr_specbank_reset_slot(self.h, int(slot)))
+
+    def try_process(self, items):
+        """items: [(slot, iq)] with iq a numpy array, a CUDA torch tensor, a DevicePointer, or None / empty for no input -> the return code"""
+        arr = (H.SpecBankItem * max(len(items), 1))()
+        keep = []
+        for k, (slot, iq) in enumerate(items):
+            arr[k].slot = int(slot)
+            if iq is None or (isinstance(iq, np.ndarray) and iq.size == 0):
+                arr[k].n, arr[k].iq, arr[k].is_dev = 0, None, 0
+                continue
+            p, is_dev, n, ka = _as_iq_arg(iq)
+            arr[k].n, arr[k].iq, arr[k].is_dev = int(n), p.value, int(is_dev)
+            keep.append(ka)
+        rc = self._l.csdr_specbank_process(self.h, arr, len(items))
+        self._keep = keep
+        return rc
+
+    def process(self, items):
+        H.check(self.try_process(items))
+
+    def process_bank(self, bank):
+        """every block of the bank's last execute, for every active slot the object has room for: one call, no host synchronisation"""
+        H.check(self._l.csdr_specbank_process_bank(self.h, bank.h))
+
+    def frames(self, slot):
+        return self._l.csdr_specbank_frames(self.h, int(slot))
+
+    def fetch(self, slot, frame):
+        pts = np.empty(2 * self.fft_size, np.float32)
+        ce, fl = C.c_double(), C.c_double()
+        H.check(self._l.csdr_specbank_fetch(self.h, int(slot), int(frame), pts.ctypes.data_as(C.c_void_p), pts.size, C.byref(ce), C.byref(fl)))
+        return pts, ce.value, fl.value
+
+    def fetch_hold(self, slot, frame):
+        """spectrum_hold_points of a frame, or None when it carries none"""
+        pts = np.empty(2 * self.fft_size, np.float32)
+        n = C.c_int()
+        H.check(self._l.csdr_specbank_fetch_hold(self.h, int(slot), int(frame), pts.ctypes.data_as(C.c_void_p), pts.size, C.byref(n)))
+        return pts if n.value else None
+
+    def device_points(self, slot):
+        """(device pointer, frames): the [frames, fft_size] y values of the slot's last call; the context's boundary stream waits for them"""
+        p, n = C.c_void_p(), C.c_int()
+        H.check(self._l.csdr_specbank_device_points(self.h, int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def close(self):
+        if self.h:
+            self._l.csdr_specbank_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 def design_gradient(stops, length=256):
     """Gradient::generate(length) for colour stops [[r, g, b], ...] (host only) -> (r, g, b) float32 arrays"""
     a = np.ascontiguousarray(stops, dtype=np.float32).reshape(-1, 3)

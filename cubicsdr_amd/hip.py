@@ -81,6 +81,10 @@ class ViewTap(C.Structure):
 WF_VIEW_LINEAR, WF_VIEW_PEAK = 0, 1
 
 
+class SpecBankItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("n", C.c_int32), ("iq", C.c_void_p), ("is_dev", C.c_int32), ("reserved", C.c_int32)]
+
+
 class P2pOp(C.Structure):
     _fields_ = [("peer", C.c_int32), ("recv", C.c_int32), ("buf", C.c_void_p), ("n_samples", C.c_int64)]
 
@@ -262,6 +266,20 @@ ABI = {
     "csdr_distrib_fetch_lines": (_i, [_p, _p, _i64, C.POINTER(_i)]),
     "csdr_distrib_fetch_buffered": (_i, [_p, _p, _i64, C.POINTER(_i)]),
     "csdr_spec_process_distrib": (_i, [_p, _p]),
+    "csdr_specbank_create": (_i, [_p, _pp]),
+    "csdr_specbank_destroy": (None, [_p]),
+    "csdr_specbank_setup": (_i, [_p, _i, _i, _i]),
+    "csdr_specbank_set_average_rate": (_i, [_p, _f]),
+    "csdr_specbank_set_scale_factor": (_i, [_p, _f]),
+    "csdr_specbank_set_peak_hold": (_i, [_p, _i]),
+    "csdr_specbank_get_peak_hold": (_i, [_p]),
+    "csdr_specbank_reset_slot": (_i, [_p, _i]),
+    "csdr_specbank_process": (_i, [_p, C.POINTER(SpecBankItem), _i]),
+    "csdr_specbank_process_bank": (_i, [_p, _p]),
+    "csdr_specbank_frames": (_i, [_p, _i]),
+    "csdr_specbank_fetch": (_i, [_p, _i, _i, _p, _i, C.POINTER(_d), C.POINTER(_d)]),
+    "csdr_specbank_fetch_hold": (_i, [_p, _i, _i, _p, _i, C.POINTER(_i)]),
+    "csdr_specbank_device_points": (_i, [_p, _i, _pp, C.POINTER(_i)]),
     "csdr_table_run": (_i, [_p, C.POINTER(Constellation), _p, _i, C.POINTER(DigitalState), _p, _i, C.POINTER(_i), C.POINTER(_f)]),
 }
 

@@ -46,6 +46,7 @@ typedef struct csdr_ingest csdr_ingest; /* page-locked block ring -> HBM, one tr
 typedef struct csdr_comm  csdr_comm;   /* one IQ stream over the GPUs of a node: RCCL over xGMI */
 typedef struct csdr_waterfall csdr_waterfall; /* WaterfallPanel's arithmetic: quantised lines, two ring textures, themed RGBA */
 typedef struct csdr_distrib csdr_distrib; /* FFTDataDistributor's line cutting: the waterfall feed, cut where the block lies in HBM */
+typedef struct csdr_specbank csdr_specbank; /* N x SpectrumVisualProcessor, one per demodulator: every slot and block of an execute in one launch */
 
 /* ------------------------------------------------------------------ context */
 int         csdr_abi_version(void);
@@ -634,6 +635,78 @@ int  csdr_distrib_fetch_buffered(csdr_distrib *d, float *host, int64_t cap_float
  * max_frames >= n_lines and csdr_spec_frames / csdr_spec_fetch / csdr_waterfall_step_spec see n_lines frames.  Zoomed view: one call per line
  * (every call is one input there).  A push that emitted no line leaves the spectrum untouched.  Both handles are used by this call. */
 int  csdr_spec_process_distrib(csdr_spec *spec, csdr_distrib *d);
+
+/* ------------------------------------------------------------------ Spectrum bank: one SpectrumVisualProcessor per demodulator
+ * The reference shows a spectrum and a waterfall of the ACTIVE demodulator (CubicSDR.cpp:373-381, DEFAULT_DMOD_FFT_SIZE 1024): one
+ * SpectrumVisualProcessor fed the demodulator's resampled IQ.  A csdr_specbank holds max_slots of them, all of one fft_size F (internal size
+ * Fi = 2 F: SPECTRUM_VZM, SpectrumVisualProcessor.h:11); the state of every slot and the points of every frame stay in HBM, and one call runs all
+ * slots and all inputs it is given in ONE kernel launch.  Every slot behaves as one SpectrumVisualProcessor after setup(F), in full-span view
+ * (is_view false, visualRatio 1), that receives one process() input per item.  Lines are those of src/process/SpectrumVisualProcessor.cpp.
+ * 1. Limits.  F is a power of two, 8 <= F <= 2048 (Fi <= 4096 is what the transform holds in LDS); 1 <= max_slots <= 4096; max_frames >= 1 is the
+ *    number of output frames a slot can hold per call.  F < 8, max_slots or max_frames out of range: CSDR_EINVAL; an F from 8 on that is not a power
+ *    of two or exceeds 2048 -- sizes the reference takes (setFFTSize :180-190) -- CSDR_EUNSUPPORTED.  A call that would give a slot more frames than
+ *    max_frames is refused as a whole with CSDR_ERANGE: nothing is processed and no state changes.
+ * 2. Frame selection (:387-421), planned on the host per (slot, item) from the lengths alone.  lastDataSize is per slot, 0 after setup or reset.
+ *      n >= Fi: the first Fi samples are the frame and become fftLastData; lastDataSize is not touched (:401-404).
+ *      n < Fi and lastDataSize + n < Fi: priming.  num_copy = max(Fi - lastDataSize, n); fftLastData[0 .. num_copy) takes the data followed by
+ *        zeros, no frame is produced, lastDataSize += num_copy (:407-413).
+ *      otherwise the frame is fftLastData[lastDataSize - (Fi - n) .. lastDataSize) followed by the n new samples, and becomes fftLastData (:415-419).
+ *    The reference's quirk is kept: a slot whose first inputs were >= Fi long still primes on its first short input.
+ *    The library's own definition: an item with n = 0 is no input at all -- it advances no countdown and touches no state.  A block the front-end
+ *    skipped (csdr_block_result.skipped) is such an item.
+ * 3. Per frame (:437-576, :626-627), literally: the forward FFT of Fi points; the float magnitude with the half swap (:441-452); the NaN re-seeding
+ *    and the two double averagers in the reference's order (:494-498); ceiling and floor (:500-505; their `!=` halves cannot fire: a float that
+ *    only takes values through `>` / `<` never turns NaN); the four trackers at 0.05 with their re-seeding (:513-521) from 100 / 100 / 0 / 0 (:32-33);
+ *    the display points, two bins per point, bin 0 replaced by fft_floor_maa (:542-576), log10 in double; fft_ceiling = point_ceil / sf,
+ *    fft_floor = point_floor.  The average rate (default 0.65f, held as float) and the scale factor (default 1) are per object and are read by the
+ *    next process call.  Output per frame: F y values; the x of point i is (float)i / (float)F and is added by the fetch, which returns (x, y)
+ *    pairs as csdr_spec_fetch does.
+ * 4. Peak hold (:115-125, :247, :264-273, :506-510, :523-530, :539-540): a per-object setter, per-slot state.  csdr_specbank_set_peak_hold is
+ *    setPeakHold on every slot: the countdown to the reset becomes 1, or PEAK_RESET_COUNT = 30 when hold was on and is enabled again.  The
+ *    countdown is decremented per non-empty item of a slot, on the host; the reset of fft_result_peak / fft_ceil_peak / fft_floor_peak happens on
+ *    the device in front of the item it belongs to.  Hold points are fetched with csdr_specbank_fetch_hold; *n_floats = 0 when the frame carries none.
+ * 5. Slot life cycle.  csdr_specbank_reset_slot makes a slot a fresh processor on which setPeakHold(the object's setting) was called once:
+ *    averagers zero, trackers at their initial values, lastDataSize 0, the countdown at 1.  csdr_specbank_setup resets all slots (the object's
+ *    average rate, scale factor and peak-hold setting stay).  Slots are independent: what one slot is fed, and whether others are fed at all,
+ *    changes no bit of another slot's output; items of one slot are its inputs in the order given, whatever lies between them.
+ * 6. Not in this object, and refused or absent rather than approximated: the zoomed view (the reference's demodulator view zooms the CHANNEL row;
+ *    this bank shows the demodulator's own band at its own rate), hideDC, sizes that are not powers of two, F > 2048.
+ * Ordering.  All work runs on a stream of the object's own, as a waterfall's does; the fetches synchronise it.  Host inputs are staged with
+ * hipMemcpyAsync (the rule of csdr_post_execute for page-locked memory holds); device inputs must have been produced on the boundary stream.
+ * csdr_specbank_process_bank orders itself behind the bank's front-end by an event and leaves one that the bank's later executes wait for before
+ * that parity's buffers are rewritten: the two objects never synchronise the host for each other (a call waits on the host only for the upload of its
+ * plan that last used the same page-locked staging set, two calls ago).  A refused call enqueues nothing and changes nothing.
+ * The points csdr_specbank_device_points hands out are rewritten by the next process call, which waits for no reader: whoever reads them on the device
+ * has FINISHED before that call (csdr_waterfall_fetch_* or any other synchronising call on the reader's stream). */
+typedef struct csdr_specbank_item {
+    int32_t slot;              /* 0 .. max_slots - 1 */
+    int32_t n;                 /* complex samples of this process() input; 0: no input */
+    const float *iq;           /* interleaved (re, im); device memory (8-byte aligned) when is_dev != 0 */
+    int32_t is_dev;
+    int32_t reserved;
+} csdr_specbank_item;
+CSDR_STATIC_ASSERT(sizeof(csdr_specbank_item) == 24 && offsetof(csdr_specbank_item, iq) == 8 && offsetof(csdr_specbank_item, is_dev) == 16, "csdr_specbank_item layout");
+int  csdr_specbank_create(csdr_ctx *ctx, csdr_specbank **out);
+void csdr_specbank_destroy(csdr_specbank *sb);
+int  csdr_specbank_setup(csdr_specbank *sb, int fft_size, int max_slots, int max_frames);
+int  csdr_specbank_set_average_rate(csdr_specbank *sb, float rate);       /* setFFTAverageRate */
+int  csdr_specbank_set_scale_factor(csdr_specbank *sb, float sf);         /* setScaleFactor */
+int  csdr_specbank_set_peak_hold(csdr_specbank *sb, int enabled);         /* setPeakHold :115-125, on every slot */
+int  csdr_specbank_get_peak_hold(const csdr_specbank *sb);
+int  csdr_specbank_reset_slot(csdr_specbank *sb, int slot);
+/* n_items process() inputs; the items of one slot are its inputs in the order given */
+int  csdr_specbank_process(csdr_specbank *sb, const csdr_specbank_item *items, int n_items);
+/* After a csdr_bank_execute (CSDR_ESTATE before the first): every configured, active slot s < max_slots of the bank gets one item per block of that
+ * execute -- that block's resampled IQ where it lies in HBM (what csdr_bank_fetch_iq returns, cut by csdr_block_result.n_iq).  Analog, host-only
+ * (CSDR_MODEM_HOST) and digital slots alike: they all have resampled IQ.  Both handles are used by this call. */
+int  csdr_specbank_process_bank(csdr_specbank *sb, csdr_bank *bank);
+int  csdr_specbank_frames(const csdr_specbank *sb, int slot);             /* frames the last process call produced for the slot */
+/* SpectrumVisualData of frame `frame` of the slot: spectrum_points[2 F] = (x, y) pairs, fft_ceiling, fft_floor (either may be NULL) */
+int  csdr_specbank_fetch(csdr_specbank *sb, int slot, int frame, float *points_host, int cap_floats, double *fft_ceiling, double *fft_floor);
+int  csdr_specbank_fetch_hold(csdr_specbank *sb, int slot, int frame, float *hold_host, int cap_floats, int *n_floats);
+/* the y values of the slot's frames of the last call, [frames][F] floats in HBM: the boundary stream is made to wait for them, and they stay valid
+ * until the next process or setup.  The pointer csdr_waterfall_step(points, is_dev = 1, n_floats_per_line = F, n_lines = frames) takes. */
+int  csdr_specbank_device_points(csdr_specbank *sb, int slot, const float **dev, int *frames);
 
 /* ------------------------------------------------------------------ audio egress
  * csdr_mix replaces the arithmetic AND the queue rules of audioCallback (src/audio/AudioThread.cpp:88-240): sources in binding order;
