@@ -291,6 +291,7 @@ enum CsdrKernelId {
     KID_WF_QUANTIZE, KID_WF_UPDATE, KID_WF_RGBA, KID_WF_VIEW_LINEAR, KID_WF_VIEW_PEAK,
     KID_DISTRIB_GATHER,
     KID_SPECBANK,
+    KID_WFB_QUANTIZE, KID_WFB_UPDATE, KID_WFB_VIEW_LINEAR, KID_WFB_VIEW_PEAK,
     KID_COUNT
 };
 

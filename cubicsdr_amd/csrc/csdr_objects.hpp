@@ -153,6 +153,17 @@ int spec_points_acquire(csdr_spec *s, hipStream_t reader, SpecPointsRef *out);
 int spec_points_release(csdr_spec *s, hipStream_t reader);
 csdr_ctx *spec_ctx(const csdr_spec *s);      // the context a spectrum was created on (csdr_spec_process_distrib checks it against the distributor's)
 
+// The spectrum bank's counterpart (csdr_wfbank_step_specbank): the points of every slot's frames of the bank's last process, [slot][max_frames][F],
+// with the same two events.  The spectrum bank's next process, process_bank, setup or reset_slot waits for the reader before it touches them.
+// (csdr_specbank.hip; the frames of a slot are csdr_specbank_frames)
+struct SpecBankPointsRef {
+    csdr_ctx *ctx = nullptr;
+    const float *points = nullptr;           // frame f of slot s: points + ((size_t)s * max_frames + f) * F
+    int F = 0, max_slots = 0, max_frames = 0;
+};
+int specbank_points_acquire(csdr_specbank *sb, hipStream_t reader, SpecBankPointsRef *out);
+int specbank_points_release(csdr_specbank *sb, hipStream_t reader);
+
 // =================================================================================================== resampled IQ for device-side readers
 // The bank-side counterpart of the above: the slots' resampled IQ of the last execute (where csdr_bank_fetch_iq reads it), for a reader that stays in
 // HBM (csdr_specbank_process_bank).  `reader` is made to wait for the front-end of that execute by an event (no host synchronisation); after enqueueing

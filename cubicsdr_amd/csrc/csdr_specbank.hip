@@ -53,7 +53,19 @@ struct csdr_specbank {
     std::vector<int> n_jobs_of, job_at, cursor, run_slots;     // per slot: jobs of the call, its first job, the next one to fill; the slots that have jobs
     std::vector<SpecBankJob> jobs_h;
     std::vector<csdr_specbank_item> bank_items;
+    // a reader of `points` that stays on the device (specbank_points_acquire / _release: the waterfall bank's quantiser on its own stream).  Created
+    // at the first acquire: a spectrum bank nobody reads this way never has them
+    hipEvent_t ev_points_ready = nullptr, ev_points_read = nullptr;
+    bool points_reader = false;                        // ev_points_read is recorded and not yet waited for
 };
+
+// whatever rewrites the points comes behind the reader that was handed them (one test, untaken while nobody reads this way)
+static int sb_wait_reader(csdr_specbank *sb) {
+    if (!sb->points_reader) return CSDR_OK;
+    CSDR_HIP_TRY(hipStreamWaitEvent(sb->st, sb->ev_points_read, 0));
+    sb->points_reader = false;
+    return CSDR_OK;
+}
 
 extern "C" int csdr_specbank_create(csdr_ctx *ctx, csdr_specbank **out) {
     DeviceScope dev__(ctx);
@@ -78,6 +90,8 @@ extern "C" void csdr_specbank_destroy(csdr_specbank *sb) {
     if (sb->ev_in) (void)hipEventDestroy(sb->ev_in);
     if (sb->ev_out) (void)hipEventDestroy(sb->ev_out);
     for (int k = 0; k < kSbStage; ++k) { if (sb->plan_ev[k]) (void)hipEventDestroy(sb->plan_ev[k]); sb->plan_h[k].release(); }
+    if (sb->ev_points_ready) (void)hipEventDestroy(sb->ev_points_ready);
+    if (sb->ev_points_read) (void)hipEventDestroy(sb->ev_points_read);
     sb->tw4096.release(); sb->last.release(); sb->stage.release(); sb->ma.release(); sb->maa.release(); sb->peak.release(); sb->trk.release();
     sb->points.release(); sb->hold.release(); sb->meta.release(); sb->plan.release();
     delete sb;
@@ -106,6 +120,7 @@ extern "C" int csdr_specbank_setup(csdr_specbank *sb, int fft_size, int max_slot
     if ((fft_size & (fft_size - 1)) != 0 || fft_size > kFftMaxLds / 2) return fail(CSDR_EUNSUPPORTED, "fft_size %d: a power of two, 8 .. %d", fft_size, kFftMaxLds / 2);
     if (max_slots < 1 || max_slots > 4096) return fail(CSDR_EINVAL, "max_slots %d: 1 .. 4096", max_slots);
     if (max_frames < 1) return fail(CSDR_EINVAL, "max_frames %d", max_frames);
+    if (int rc = sb_wait_reader(sb)) return rc;          // (the buffers may be replaced: the synchronise below then covers the reader too)
     CSDR_HIP_TRY(hipStreamSynchronize(sb->st));
     sb->ready = false;
     const size_t Fi = 2 * (size_t)fft_size, S = (size_t)max_slots;        // SPECTRUM_VZM (.h:11, :145)
@@ -163,6 +178,7 @@ extern "C" int csdr_specbank_reset_slot(csdr_specbank *sb, int slot) {
     DeviceScope dev__(sb ? sb->ctx : nullptr);
     if (!sb || !sb->ready) return fail(CSDR_ESTATE, "spectrum bank not set up");
     if (slot < 0 || slot >= sb->max_slots) return fail(CSDR_EINVAL, "slot %d of %d", slot, sb->max_slots);
+    if (int rc = sb_wait_reader(sb)) return rc;
     return sb_reset_slot(sb, slot);
 }
 
@@ -221,6 +237,7 @@ static int sb_run(csdr_specbank *sb, const csdr_specbank_item *items, int n_item
     for (int s : sb->run_slots) sb->slots[(size_t)s] = sb->work[(size_t)s];
     sb->sf_last = sb->sf;
     if (n_jobs == 0) return CSDR_OK;
+    if (int rc = sb_wait_reader(sb)) return rc;
     if (bank) if (int rc = bank_iq_acquire(bank, sb->st)) return rc;
     if (any_dev) {
         CSDR_HIP_TRY(hipEventRecord(sb->ev_in, sb->ctx->stream));
@@ -371,5 +388,23 @@ extern "C" int csdr_specbank_device_points(csdr_specbank *sb, int slot, const fl
     CSDR_HIP_TRY(hipStreamWaitEvent(sb->ctx->stream, sb->ev_out, 0));
     *dev = sb->points.p + (size_t)slot * (size_t)sb->max_frames * (size_t)sb->F;
     if (frames) *frames = sb->slots[(size_t)slot].frames;
+    return CSDR_OK;
+}
+
+// ---- the points for a reader that stays on the device (csdr_objects.hpp) ----
+int specbank_points_acquire(csdr_specbank *sb, hipStream_t reader, SpecBankPointsRef *out) {
+    if (!sb || !sb->ready || !out) return fail(CSDR_ESTATE, "spectrum bank not set up");
+    if (!sb->ev_points_ready) {
+        CSDR_HIP_TRY(hipEventCreateWithFlags(&sb->ev_points_ready, hipEventDisableTiming));
+        CSDR_HIP_TRY(hipEventCreateWithFlags(&sb->ev_points_read, hipEventDisableTiming));
+    }
+    CSDR_HIP_TRY(hipEventRecord(sb->ev_points_ready, sb->st));
+    CSDR_HIP_TRY(hipStreamWaitEvent(reader, sb->ev_points_ready, 0));
+    out->ctx = sb->ctx; out->points = sb->points.p; out->F = sb->F; out->max_slots = sb->max_slots; out->max_frames = sb->max_frames;
+    return CSDR_OK;
+}
+int specbank_points_release(csdr_specbank *sb, hipStream_t reader) {
+    CSDR_HIP_TRY(hipEventRecord(sb->ev_points_read, reader));
+    sb->points_reader = true;
     return CSDR_OK;
 }

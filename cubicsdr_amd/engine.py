@@ -694,6 +694,107 @@ class Waterfall:
             self.h = C.c_void_p()
 
 
+class WaterfallBank:
+    """N independent WaterfallPanels of one fft_size and one `lines` (csdr_wfbank): one per demodulator; every slot of a step, an update or a
+    render in one launch; lines, textures and pictures stay in HBM."""
+
+    def __init__(self, ctx, fft_size, lines, max_slots, max_pending=256):
+        self._l = H.lib()
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        H.check(self._l.csdr_wfbank_create(ctx.h, C.byref(self.h)))
+        self.setup(fft_size, lines, max_slots, max_pending)
+
+    def setup(self, fft_size, lines, max_slots, max_pending=256):
+        H.check(self._l.csdr_wfbank_setup(self.h, int(fft_size), int(lines), int(max_slots), int(max_pending)))
+        self.fft_size, self.half, self.lines, self.max_slots = int(fft_size), int(fft_size) // 2, int(lines), int(max_slots)
+
+    def set_gradient(self, stops):
+        a = np.ascontiguousarray(stops, dtype=np.float32).reshape(-1, 3)
+        H.check(self._l.csdr_wfbank_set_gradient(self.h, a.ctypes.data_as(C.c_void_p), int(a.shape[0])))
+
+    def reset_slot(self, slot):
+        H.check(self._l.csdr_wfbank_reset_slot(self.h, int(slot)))
+
+    def try_step(self, items):
+        """items: [(slot, points)] or [(slot, None, n_lines)] -- points None (repeat the slot's previous points n_lines times), a numpy float32
+        array [n_lines, n] / [n], or a CUDA torch tensor of that shape -> (return code, [lines taken per item])"""
+        arr = (H.WfBankItem * max(len(items), 1))()
+        taken = (C.c_int * max(len(items), 1))()
+        keep = []
+        for k, it in enumerate(items):
+            slot, points = it[0], it[1]
+            arr[k].slot = int(slot)
+            if points is None:
+                arr[k].n_floats_per_line, arr[k].points, arr[k].is_dev, arr[k].n_lines = 0, None, 0, int(it[2]) if len(it) > 2 else 1
+                continue
+            if isinstance(points, np.ndarray):
+                a = np.ascontiguousarray(points, dtype=np.float32)
+                ptr, is_dev, shape = a.ctypes.data, 0, a.shape
+            else:
+                a = points.contiguous()
+                ptr, is_dev, shape = a.data_ptr(), 1, tuple(a.shape)
+            arr[k].n_floats_per_line, arr[k].points, arr[k].is_dev = int(shape[-1]), ptr, is_dev
+            arr[k].n_lines = 1 if len(shape) == 1 else int(shape[0])
+            keep.append(a)
+        rc = self._l.csdr_wfbank_step(self.h, arr, len(items), taken)
+        self._keep = keep
+        return rc, [taken[k] for k in range(len(items))]
+
+    def step(self, items):
+        rc, taken = self.try_step(items)
+        H.check(rc)
+        return taken
+
+    def step_from(self, specbank):
+        """the frames of every slot of the SpectrumBank's last process, straight from its points in HBM: one call, no host synchronisation ->
+        the lines taken over all slots"""
+        total = C.c_int()
+        H.check(self._l.csdr_wfbank_step_specbank(self.h, specbank.h, C.byref(total)))
+        return total.value
+
+    def update(self):
+        H.check(self._l.csdr_wfbank_update(self.h))
+
+    def lines_buffered(self, slot):
+        return self._l.csdr_wfbank_lines_buffered(self.h, int(slot))
+
+    def offset(self, slot, half=0):
+        return self._l.csdr_wfbank_offset(self.h, int(slot), int(half))
+
+    def fetch_index(self, slot, half):
+        out = np.empty((self.lines, self.half), np.uint8)
+        H.check(self._l.csdr_wfbank_fetch_index(self.h, int(slot), int(half), out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def view(self, slots, width, height, mode="linear", atlas_cols=1, fetch=True):
+        """the listed slots' rings scaled to width x height tiles of one picture, [tile rows * height, atlas_cols * width, 4] uint8; slots: a list, or
+        an int n for slots 0 .. n - 1; fetch=False renders it and leaves it on the device (device_view)"""
+        if isinstance(slots, (int, np.integer)):
+            n, lst = int(slots), None
+        else:
+            n = len(slots)
+            lst = (C.c_int * max(n, 1))(*[int(s) for s in slots])
+        if not fetch:
+            H.check(self._l.csdr_wfbank_render(self.h, lst, n, int(width), int(height), _view_mode(mode), int(atlas_cols), None, 0))
+            return None
+        tile_rows = -(-n // max(int(atlas_cols), 1))
+        out = np.empty((max(tile_rows * int(height), 0), max(int(atlas_cols) * int(width), 0), 4), np.uint8)
+        H.check(self._l.csdr_wfbank_render(self.h, lst, n, int(width), int(height), _view_mode(mode), int(atlas_cols), out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def device_view(self):
+        """(device pointer, width, height) of the last rendered picture in pixels; the context's boundary stream waits for it"""
+        p, w, h = C.c_void_p(), C.c_int(), C.c_int()
+        H.check(self._l.csdr_wfbank_device_view(self.h, C.byref(p), C.byref(w), C.byref(h)))
+        return p.value, w.value, h.value
+
+    def close(self):
+        if self.h:
+            self._l.csdr_wfbank_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class Distributor:
     """FFTDataDistributor's line cutting (csdr_distrib): the waterfall feed, cut where the block lies in HBM."""
 

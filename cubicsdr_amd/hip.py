@@ -85,6 +85,10 @@ class SpecBankItem(C.Structure):
     _fields_ = [("slot", C.c_int32), ("n", C.c_int32), ("iq", C.c_void_p), ("is_dev", C.c_int32), ("reserved", C.c_int32)]
 
 
+class WfBankItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("n_floats_per_line", C.c_int32), ("points", C.c_void_p), ("is_dev", C.c_int32), ("n_lines", C.c_int32)]
+
+
 class P2pOp(C.Structure):
     _fields_ = [("peer", C.c_int32), ("recv", C.c_int32), ("buf", C.c_void_p), ("n_samples", C.c_int64)]
 
@@ -280,6 +284,19 @@ ABI = {
     "csdr_specbank_fetch": (_i, [_p, _i, _i, _p, _i, C.POINTER(_d), C.POINTER(_d)]),
     "csdr_specbank_fetch_hold": (_i, [_p, _i, _i, _p, _i, C.POINTER(_i)]),
     "csdr_specbank_device_points": (_i, [_p, _i, _pp, C.POINTER(_i)]),
+    "csdr_wfbank_create": (_i, [_p, _pp]),
+    "csdr_wfbank_destroy": (None, [_p]),
+    "csdr_wfbank_setup": (_i, [_p, _i, _i, _i, _i]),
+    "csdr_wfbank_set_gradient": (_i, [_p, _p, _i]),
+    "csdr_wfbank_reset_slot": (_i, [_p, _i]),
+    "csdr_wfbank_step": (_i, [_p, C.POINTER(WfBankItem), _i, C.POINTER(_i)]),
+    "csdr_wfbank_step_specbank": (_i, [_p, _p, C.POINTER(_i)]),
+    "csdr_wfbank_update": (_i, [_p]),
+    "csdr_wfbank_lines_buffered": (_i, [_p, _i]),
+    "csdr_wfbank_offset": (_i, [_p, _i, _i]),
+    "csdr_wfbank_fetch_index": (_i, [_p, _i, _i, _p, _i64]),
+    "csdr_wfbank_render": (_i, [_p, C.POINTER(_i), _i, _i, _i, _i, _i, _p, _i64]),
+    "csdr_wfbank_device_view": (_i, [_p, _pp, C.POINTER(_i), C.POINTER(_i)]),
     "csdr_table_run": (_i, [_p, C.POINTER(Constellation), _p, _i, C.POINTER(DigitalState), _p, _i, C.POINTER(_i), C.POINTER(_f)]),
 }
 

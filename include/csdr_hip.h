@@ -47,6 +47,7 @@ typedef struct csdr_comm  csdr_comm;   /* one IQ stream over the GPUs of a node:
 typedef struct csdr_waterfall csdr_waterfall; /* WaterfallPanel's arithmetic: quantised lines, two ring textures, themed RGBA */
 typedef struct csdr_distrib csdr_distrib; /* FFTDataDistributor's line cutting: the waterfall feed, cut where the block lies in HBM */
 typedef struct csdr_specbank csdr_specbank; /* N x SpectrumVisualProcessor, one per demodulator: every slot and block of an execute in one launch */
+typedef struct csdr_wfbank csdr_wfbank;     /* N x WaterfallPanel, one per demodulator: every slot of a step, an update or a render in one launch */
 
 /* ------------------------------------------------------------------ context */
 int         csdr_abi_version(void);
@@ -676,8 +677,10 @@ int  csdr_spec_process_distrib(csdr_spec *spec, csdr_distrib *d);
  * csdr_specbank_process_bank orders itself behind the bank's front-end by an event and leaves one that the bank's later executes wait for before
  * that parity's buffers are rewritten: the two objects never synchronise the host for each other (a call waits on the host only for the upload of its
  * plan that last used the same page-locked staging set, two calls ago).  A refused call enqueues nothing and changes nothing.
- * The points csdr_specbank_device_points hands out are rewritten by the next process call, which waits for no reader: whoever reads them on the device
- * has FINISHED before that call (csdr_waterfall_fetch_* or any other synchronising call on the reader's stream). */
+ * The points are rewritten by the next process call.  ONE reader is waited for: csdr_wfbank_step_specbank ("Waterfall bank" below) leaves an event
+ * behind its reads, and the next process, process_bank, setup or reset_slot waits for it on the device.  Any other reader of the pointer
+ * csdr_specbank_device_points hands out is still not waited for: it has FINISHED before that call (csdr_waterfall_fetch_* or any other synchronising
+ * call on the reader's stream). */
 typedef struct csdr_specbank_item {
     int32_t slot;              /* 0 .. max_slots - 1 */
     int32_t n;                 /* complex samples of this process() input; 0: no input */
@@ -707,6 +710,72 @@ int  csdr_specbank_fetch_hold(csdr_specbank *sb, int slot, int frame, float *hol
 /* the y values of the slot's frames of the last call, [frames][F] floats in HBM: the boundary stream is made to wait for them, and they stay valid
  * until the next process or setup.  The pointer csdr_waterfall_step(points, is_dev = 1, n_floats_per_line = F, n_lines = frames) takes. */
 int  csdr_specbank_device_points(csdr_specbank *sb, int slot, const float **dev, int *frames);
+
+/* ------------------------------------------------------------------ Waterfall bank: one WaterfallPanel per demodulator
+ * The reference draws the demodulator waterfall (DEFAULT_DMOD_FFT_SIZE 1024 x DEFAULT_DEMOD_WATERFALL_LINES_NB lines) of the ACTIVE demodulator:
+ * one WaterfallPanel (src/panel/WaterfallPanel.cpp) fed by WaterfallCanvas::processInputQueue (src/visual/WaterfallCanvas.cpp:89-126).  A csdr_wfbank
+ * holds max_slots of them, all of one fft_size and one `lines`; every slot's pending lines, kept points, two ring textures and picture stay in HBM,
+ * and a step, an update or a render runs ALL the slots it concerns in ONE kernel launch.  Every slot behaves exactly as one csdr_waterfall does:
+ * items 1 - 7 of "WaterfallPanel" and items 1 - 5 of "Waterfall viewport" above hold per slot, the reference's quirks (row lines - 1 unwritten during
+ * the first turn, the older remainder above the newer run when an update crosses the wrap) and the library's own definitions (NaN -> index 0, the
+ * texel rounding, which half a pixel shows, the LINEAR blend, the PEAK footprints) included.  What is per object and what per slot:
+ * 1. Limits (setup :13-24 on every slot).  2 <= fft_size <= 4096, any value, half = fft_size / 2 <= 2048 (an odd last point is not drawn);
+ *    2 <= lines <= 4096; 1 <= max_slots <= 4096; max_pending >= 1 lines may wait per slot; anything else is CSDR_EINVAL.  Per slot a setup clears
+ *    lines_buffered, marks the textures uninitialised and keeps the points (:18-20: resized, new ones zero; a slot the object did not have before
+ *    starts with zero points).  csdr_wfbank_reset_slot leaves ONE slot as after a setup, with its points zero; its neighbours are untouched.
+ * 2. Gradient (item 5 above): one table for the object, the grey ramp before any csdr_wfbank_set_gradient; it outlives a setup.
+ * 3. step.  An item is n_lines lines of n_floats_per_line floats for one slot: setPoints + step (:39-83) for each, with both line layouts, the
+ *    wrong-length or NULL line that repeats the slot's previous points, and the steps dropped before the slot's first update -- their points are
+ *    still kept -- as items 2 and 3 above state them, per slot.  The items of a slot are stepped in the order given, whatever lies between them;
+ *    a wrong-length line directly behind a good one of the same call repeats that good line.  taken[i] (taken may be NULL) = the lines item i put
+ *    into its slot's pending buffer.  A call that would leave ANY slot with more than max_pending lines waiting (CSDR_ERANGE), or that names a slot
+ *    out of range (CSDR_EINVAL), is refused as a whole: it enqueues nothing and changes nothing, in no slot.
+ * 4. step_specbank.  For every slot s below the smaller of the two objects' slot counts: the csdr_specbank_frames(sb, s) frames of the spectrum
+ *    bank's last process, in frame order, straight from its point buffer in HBM -- one item per slot.  A spectrum bank whose fftSize is not fft_size
+ *    delivers frames of the wrong size (item 2 above), as csdr_waterfall_step_spec defines for a spectrum.  *taken_total (may be NULL) = the lines
+ *    taken over all slots.  What csdr_specbank_fetch returns is not changed by it.
+ * 5. update is WaterfallPanel::update (:85-159) on every slot, and the panels are independent: a slot with at least one step call since its setup
+ *    and no textures gets both rings zero-filled with waterfall_ofs = lines - 1; a slot with pending lines has them written by the reference's loop
+ *    (item 4 above); a slot that was never stepped stays without textures.  So the slots' offsets differ as soon as their histories do.
+ * 6. render is drawPanelContents (:161-219) of every listed slot scaled to width x height (limits and modes: viewport item 1; fft_size >= 4),
+ *    as ONE dense RGBA8 picture of ceil(n_slots / atlas_cols) * height rows by atlas_cols * width pixels: the tile of list entry k lies at tile row
+ *    k / atlas_cols, tile column k % atlas_cols, so atlas_cols = 1 gives [n_slots][height][width].  slots == NULL means slots 0 .. n_slots - 1
+ *    (n_slots <= max_slots then); a slot may appear more than once; 1 <= atlas_cols <= n_slots <= 2^20.  A tile is byte for byte what
+ *    csdr_waterfall_render_view(width, height, mode) gives for a waterfall in that slot's state; with width = 2 half, height = lines and PEAK it
+ *    equals csdr_waterfall_fetch_rgba(0, lines), so there is no separate unscaled call.  THE LIBRARY'S OWN DEFINITION: the tile of a slot without
+ *    textures (the reference draws nothing, :162-164) and the unused tiles of the last tile row are all-zero bytes -- transparent black --
+ *    rewritten on every call.  out_u8 == NULL leaves the picture on the device; otherwise it is copied and the stream synchronised; too small a cap
+ *    is CSDR_ERANGE.  A refusal renders nothing and changes nothing.  csdr_wfbank_device_view returns the last rendered picture and its size in
+ *    pixels and makes the context's boundary stream wait for it; it stays valid until the next render or setup.
+ * Ordering.  All work runs on a stream of the object's own; csdr_wfbank_fetch_index and a render into host memory synchronise it.  Host lines are
+ * copied into page-locked staging inside the call, so the caller's buffer is free when it returns; device lines must have been produced on the
+ * boundary stream, are ordered behind it by an event and stay unchanged until the next synchronising call on this object.  step_specbank makes the
+ * object's stream wait for the spectrum bank's kernel by an event and leaves one that the spectrum bank's next process, process_bank, setup or
+ * reset_slot waits for before it rewrites the points: the two objects never synchronise the host for each other.  A call waits on the host only for
+ * the upload of its records that last used the same page-locked staging set, two calls ago. */
+typedef struct csdr_wfbank_item {
+    int32_t slot;              /* 0 .. max_slots - 1 */
+    int32_t n_floats_per_line; /* fft_size, or 2 * fft_size for (x, y) pairs; anything else repeats the slot's previous points */
+    const float *points;       /* n_lines lines, dense; device memory (4-byte aligned) when is_dev != 0; NULL repeats the previous points */
+    int32_t is_dev;
+    int32_t n_lines;           /* 0: nothing, not even a step call */
+} csdr_wfbank_item;
+CSDR_STATIC_ASSERT(sizeof(csdr_wfbank_item) == 24 && offsetof(csdr_wfbank_item, points) == 8 && offsetof(csdr_wfbank_item, is_dev) == 16 &&
+                   offsetof(csdr_wfbank_item, n_lines) == 20, "csdr_wfbank_item layout");
+int  csdr_wfbank_create(csdr_ctx *ctx, csdr_wfbank **out);
+void csdr_wfbank_destroy(csdr_wfbank *wb);
+int  csdr_wfbank_setup(csdr_wfbank *wb, int fft_size, int lines, int max_slots, int max_pending);
+int  csdr_wfbank_set_gradient(csdr_wfbank *wb, const float *rgb_stops, int n_colors);        /* csdr_design_gradient's stops, as csdr_waterfall_set_gradient */
+int  csdr_wfbank_reset_slot(csdr_wfbank *wb, int slot);
+int  csdr_wfbank_step(csdr_wfbank *wb, const csdr_wfbank_item *items, int n_items, int *taken);      /* taken[n_items], may be NULL */
+int  csdr_wfbank_step_specbank(csdr_wfbank *wb, csdr_specbank *sb, int *taken_total);        /* both handles are used by this call */
+int  csdr_wfbank_update(csdr_wfbank *wb);                                                    /* WaterfallPanel::update on every slot */
+int  csdr_wfbank_lines_buffered(const csdr_wfbank *wb, int slot);
+int  csdr_wfbank_offset(const csdr_wfbank *wb, int slot, int half);                          /* waterfall_ofs[half] of the slot; -1 while it has no textures */
+/* one ring texture of one slot: lines x (fft_size / 2) bytes, rows as GL holds them (synchronises); CSDR_ESTATE while the slot has no textures */
+int  csdr_wfbank_fetch_index(csdr_wfbank *wb, int slot, int half, uint8_t *out_u8, int64_t cap);
+int  csdr_wfbank_render(csdr_wfbank *wb, const int *slots, int n_slots, int width, int height, int mode, int atlas_cols, uint8_t *out_u8, int64_t cap);
+int  csdr_wfbank_device_view(csdr_wfbank *wb, const uint8_t **dev, int *pic_width, int *pic_height);
 
 /* ------------------------------------------------------------------ audio egress
  * csdr_mix replaces the arithmetic AND the queue rules of audioCallback (src/audio/AudioThread.cpp:88-240): sources in binding order;
