@@ -107,6 +107,43 @@ struct PinBuf {
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
 
+// A call's records on their way to the device: N page-locked staging sets, used in turn, in front of ONE device buffer on ONE stream.  A call fills
+// host() between begin() and uploaded(); the kernels behind it on the stream read device().  The one host wait of a call is begin()'s: for the upload
+// that last used this set, N calls ago.
+template <int N>
+class StageRing {
+    DevBuf<char> dev;
+    PinBuf<char> set[N];
+    hipEvent_t ev[N] = {};
+    bool used[N] = {};
+    int next = 0, cur = 0;
+public:
+    int create() {
+        for (int k = 0; k < N; ++k) CSDR_HIP_TRY(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+        return CSDR_OK;
+    }
+    void destroy() {
+        for (int k = 0; k < N; ++k) { if (ev[k]) (void)hipEventDestroy(ev[k]); ev[k] = nullptr; set[k].release(); }
+        dev.release();
+    }
+    char *host() const { return set[cur].p; }            // the set begin() chose
+    char *device() const { return dev.p; }
+    int begin(hipStream_t st, size_t bytes) {
+        cur = next;
+        next = (next + 1) % N;
+        if (used[cur]) { CSDR_HIP_TRY(hipEventSynchronize(ev[cur])); used[cur] = false; }
+        if (int rc = set[cur].reserve(bytes)) return rc;
+        if (bytes > dev.cap) CSDR_HIP_TRY(hipStreamSynchronize(st));             // (a kernel may still read the buffer being replaced)
+        return dev.reserve(bytes);
+    }
+    int uploaded(hipStream_t st, size_t bytes) {
+        CSDR_HIP_TRY(hipMemcpyAsync(dev.p, set[cur].p, bytes, hipMemcpyHostToDevice, st));
+        CSDR_HIP_TRY(hipEventRecord(ev[cur], st));
+        used[cur] = true;
+        return CSDR_OK;
+    }
+};
+
 // one AudioThreadInput (a block) of the float -> 16-bit PCM conversion (kernels_io.hpp: pcm16_convert)
 struct PcmJob { const float *src; int16_t *dst; int32_t n; int32_t pad; const float *peak; };
 

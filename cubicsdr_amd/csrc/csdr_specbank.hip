@@ -42,11 +42,7 @@ struct csdr_specbank {
     DevBuf<SpecBankTrk> trk;
     DevBuf<float> points, hold;
     DevBuf<SpecBankFrame> meta;
-    DevBuf<char> plan;                                 // SpecBankRun [runs] | SpecBankJob [jobs] of the call being run
-    PinBuf<char> plan_h[kSbStage];
-    hipEvent_t plan_ev[kSbStage] = {nullptr, nullptr};
-    bool plan_used[kSbStage] = {false, false};
-    int plan_next = 0;
+    StageRing<kSbStage> plan;                          // SpecBankRun [runs] | SpecBankJob [jobs] of the call being run
     SpecBankTrk trk0{};                                // a fresh processor's trackers (the source of csdr_specbank_reset_slot's copy: stays)
     // scratch of a call's planning
     std::vector<SbSlot> work;
@@ -75,7 +71,7 @@ extern "C" int csdr_specbank_create(csdr_ctx *ctx, csdr_specbank **out) {
     CSDR_HIP_TRY(hipStreamCreateWithFlags(&sb->st, hipStreamNonBlocking));
     CSDR_HIP_TRY(hipEventCreateWithFlags(&sb->ev_in, hipEventDisableTiming));
     CSDR_HIP_TRY(hipEventCreateWithFlags(&sb->ev_out, hipEventDisableTiming));
-    for (int k = 0; k < kSbStage; ++k) CSDR_HIP_TRY(hipEventCreateWithFlags(&sb->plan_ev[k], hipEventDisableTiming));
+    if (int rc = sb->plan.create()) return rc;
     sb->trk0.ceil_ma = sb->trk0.ceil_maa = 100.0;       // ctor :32
     sb->trk0.floor_ma = sb->trk0.floor_maa = 0.0;       // ctor :33
     sb->trk0.ceil_peak = sb->trk0.floor_peak = 0.0;     // (written by the reset of :264-273 before anything reads them)
@@ -89,11 +85,11 @@ extern "C" void csdr_specbank_destroy(csdr_specbank *sb) {
     if (sb->st) { (void)hipStreamSynchronize(sb->st); (void)hipStreamDestroy(sb->st); }
     if (sb->ev_in) (void)hipEventDestroy(sb->ev_in);
     if (sb->ev_out) (void)hipEventDestroy(sb->ev_out);
-    for (int k = 0; k < kSbStage; ++k) { if (sb->plan_ev[k]) (void)hipEventDestroy(sb->plan_ev[k]); sb->plan_h[k].release(); }
+    sb->plan.destroy();
     if (sb->ev_points_ready) (void)hipEventDestroy(sb->ev_points_ready);
     if (sb->ev_points_read) (void)hipEventDestroy(sb->ev_points_read);
     sb->tw4096.release(); sb->last.release(); sb->stage.release(); sb->ma.release(); sb->maa.release(); sb->peak.release(); sb->trk.release();
-    sb->points.release(); sb->hold.release(); sb->meta.release(); sb->plan.release();
+    sb->points.release(); sb->hold.release(); sb->meta.release();
     delete sb;
 }
 
@@ -263,24 +259,17 @@ static int sb_run(csdr_specbank *sb, const csdr_specbank_item *items, int n_item
     }
     const size_t n_runs = sb->run_slots.size();
     const size_t bytes = n_runs * sizeof(SpecBankRun) + n_jobs * sizeof(SpecBankJob);
-    const int k = sb->plan_next;
-    sb->plan_next = (sb->plan_next + 1) % kSbStage;
-    if (sb->plan_used[k]) CSDR_HIP_TRY(hipEventSynchronize(sb->plan_ev[k]));                 // the one host wait of a call: for the upload that last used this staging set, kSbStage calls ago
-    if (int rc = sb->plan_h[k].reserve(bytes)) return rc;
-    if (bytes > sb->plan.cap) CSDR_HIP_TRY(hipStreamSynchronize(sb->st));
-    if (int rc = sb->plan.reserve(bytes)) return rc;
-    SpecBankRun *runs_h = reinterpret_cast<SpecBankRun *>(sb->plan_h[k].p);
+    if (int rc = sb->plan.begin(sb->st, bytes)) return rc;           // the one host wait of a call
+    SpecBankRun *runs_h = reinterpret_cast<SpecBankRun *>(sb->plan.host());
     for (size_t r = 0; r < n_runs; ++r) {
         const int s = sb->run_slots[r];
         runs_h[r] = SpecBankRun{s, sb->job_at[(size_t)s], sb->n_jobs_of[(size_t)s], 0};
     }
-    memcpy(sb->plan_h[k].p + n_runs * sizeof(SpecBankRun), sb->jobs_h.data(), n_jobs * sizeof(SpecBankJob));
-    CSDR_HIP_TRY(hipMemcpyAsync(sb->plan.p, sb->plan_h[k].p, bytes, hipMemcpyHostToDevice, sb->st));
-    CSDR_HIP_TRY(hipEventRecord(sb->plan_ev[k], sb->st));
-    sb->plan_used[k] = true;
+    memcpy(sb->plan.host() + n_runs * sizeof(SpecBankRun), sb->jobs_h.data(), n_jobs * sizeof(SpecBankJob));
+    if (int rc = sb->plan.uploaded(sb->st, bytes)) return rc;
     SpecBankArgs a{};
-    a.runs = reinterpret_cast<const SpecBankRun *>(sb->plan.p);
-    a.jobs = reinterpret_cast<const SpecBankJob *>(sb->plan.p + n_runs * sizeof(SpecBankRun));
+    a.runs = reinterpret_cast<const SpecBankRun *>(sb->plan.device());
+    a.jobs = reinterpret_cast<const SpecBankJob *>(sb->plan.device() + n_runs * sizeof(SpecBankRun));
     a.tw4096 = sb->tw4096.p;
     a.last = sb->last.p; a.ma = sb->ma.p; a.maa = sb->maa.p; a.peak = sb->peak.p; a.trk = sb->trk.p;
     a.points = sb->points.p; a.hold = sb->hold.p; a.meta = sb->meta.p;

@@ -8,6 +8,7 @@
 
 #define CSDR_TU_WATERFALL 1     // this unit is the home of its kernels (kernels_waterfall.hpp)
 #include "csdr_objects.hpp"
+#include "waterfall_host.hpp"
 
 using namespace csdr;
 
@@ -26,10 +27,8 @@ struct csdr_waterfall {
     DevBuf<uint32_t> table, image;                     // the 256-entry RGBA8 table; the last rendered picture
     int64_t image_pixels = 0;
     // the viewport (csdr_waterfall_render_view): tap tables per (geometry, width, height, mode) -- they do not depend on ofs -- and a picture of its own
-    DevBuf<csdr_view_tap> taps;                        // [width] columns, then [height] rows
-    std::vector<csdr_view_tap> taps_host;              // (the upload's source: stays until the next rebuild)
+    WfTapCache taps;
     DevBuf<uint32_t> view;
-    int taps_w = 0, taps_h = 0, taps_mode = -1;        // what `taps` was designed for; taps_mode -1: nothing
     int view_w = 0, view_h = 0;                        // the last rendered view; 0: none
     int peak_tile[2] = {0, 0}, peak_slots = 0;         // wf_view_peak's tiling for `taps`
     uint8_t *pend_of(int j) const { return pend.p + (size_t)j * max_pending * pitch; }
@@ -38,12 +37,6 @@ struct csdr_waterfall {
 
 #define WF_LAUNCH(w_, kid_, kern_, grid_, lds_, ...) \
     do { ProfScope ps__((w_)->ctx, (kid_), (w_)->st); hipLaunchKernelGGL(kern_, grid_, dim3(kWfThreads), lds_, (w_)->st, __VA_ARGS__); } while (0)
-
-static int wf_upload_table(csdr_waterfall *w, const uint32_t *t) {
-    CSDR_HIP_TRY(hipMemcpyAsync(w->table.p, t, 256 * sizeof(uint32_t), hipMemcpyHostToDevice, w->st));
-    CSDR_HIP_TRY(hipStreamSynchronize(w->st));          // (t is the caller's stack)
-    return CSDR_OK;
-}
 
 extern "C" int csdr_waterfall_create(csdr_ctx *ctx, csdr_waterfall **out) {
     DeviceScope dev__(ctx);
@@ -54,9 +47,7 @@ extern "C" int csdr_waterfall_create(csdr_ctx *ctx, csdr_waterfall **out) {
     CSDR_HIP_TRY(hipEventCreateWithFlags(&w->ev_in, hipEventDisableTiming));
     CSDR_HIP_TRY(hipEventCreateWithFlags(&w->ev_out, hipEventDisableTiming));
     if (int rc = w->table.reserve(256)) return rc;
-    uint32_t grey[256];                                  // before any csdr_waterfall_set_gradient: i -> (i, i, i, 255)
-    for (uint32_t i = 0; i < 256; ++i) grey[i] = i | (i << 8) | (i << 16) | 0xff000000u;
-    if (int rc = wf_upload_table(w.get(), grey)) return rc;
+    if (int rc = wf_upload_grey_table(w->st, w->table.p)) return rc;        // before any csdr_waterfall_set_gradient
     *out = w.release();
     return CSDR_OK;
 }
@@ -67,7 +58,7 @@ extern "C" void csdr_waterfall_destroy(csdr_waterfall *w) {
     if (w->st) { (void)hipStreamSynchronize(w->st); (void)hipStreamDestroy(w->st); }
     if (w->ev_in) (void)hipEventDestroy(w->ev_in);
     if (w->ev_out) (void)hipEventDestroy(w->ev_out);
-    w->points.release(); w->stage.release(); w->pend.release(); w->ring.release(); w->table.release(); w->image.release(); w->taps.release(); w->view.release();
+    w->points.release(); w->stage.release(); w->pend.release(); w->ring.release(); w->table.release(); w->image.release(); w->taps.dev.release(); w->view.release();
     delete w;
 }
 
@@ -98,7 +89,7 @@ extern "C" int csdr_waterfall_setup(csdr_waterfall *w, int fft_size, int lines, 
     w->lines_buffered = 0;                               // :16
     w->tex_init = false; w->buffer_init = false;         // :22-23
     w->image_pixels = 0;
-    w->taps_mode = -1; w->view_w = w->view_h = 0;
+    w->taps.forget(); w->view_w = w->view_h = 0;
     w->ready = true;
     return CSDR_OK;
 }
@@ -115,7 +106,7 @@ extern "C" int csdr_waterfall_set_gradient(csdr_waterfall *w, const float *rgb_s
     if (!w) return fail(CSDR_EINVAL, "waterfall is null");
     uint32_t t[256];
     if (!design::gradient_rgba8(rgb_stops, n_colors, t)) return fail(CSDR_EINVAL, "gradient: %d stops (2 .. 257, no null pointer)", n_colors);
-    return wf_upload_table(w, t);
+    return wf_upload_table(w->st, w->table.p, t);
 }
 
 // setPoints (:39-49) + step (:51-83) for n_lines lines that lie at src (device memory, ordered on w->st); valid = 0: the previous points, n_lines times
@@ -148,10 +139,8 @@ extern "C" int csdr_waterfall_step(csdr_waterfall *w, const float *points, int i
     if (taken) *taken = 0;
     if (!w || !w->ready) return fail(CSDR_ESTATE, "waterfall not set up");
     if (n_lines < 0 || n_floats_per_line < 0) return fail(CSDR_EINVAL, "bad line arguments");
-    // 2 fft_size floats: the (x, y) pairs of SpectrumVisualData (:40-45); fft_size floats: as they stand (:47); anything else leaves the points alone
-    // (WaterfallCanvas.cpp:106-109) and the step repeats them
-    const int pair = n_floats_per_line == 2 * w->fft_size ? 1 : 0;
-    const int valid = points && (pair || n_floats_per_line == w->fft_size) ? 1 : 0;
+    const int pair = wf_line_is_pairs(n_floats_per_line, w->fft_size) ? 1 : 0;
+    const int valid = wf_good_line(points, n_floats_per_line, w->fft_size) ? 1 : 0;        // (a line of another length: the step repeats the points)
     const float *src = points;
     if (valid && n_lines > 0) {
         if (!w->tex_init || w->lines_buffered + (int64_t)n_lines <= w->max_pending) {      // (a refused call moves nothing)
@@ -199,29 +188,16 @@ extern "C" int csdr_waterfall_update(csdr_waterfall *w) {
     }
     const int n = w->lines_buffered;
     if (n == 0) return CSDR_OK;
-    // :139-158 literally: runs of min(lines_buffered, waterfall_ofs[0]) rows at [ofs - run, ofs), an offset that reaches 0 becomes waterfall_lines
-    std::vector<WfRun> runs;
-    int run_ofs = 0, left = n, ofs[2] = {w->ofs[0], w->ofs[1]};
-    while (left) {
-        int run_lines = left;
-        if (run_lines > ofs[0]) run_lines = ofs[0];
-        runs.push_back(WfRun{run_ofs, ofs[0] - run_lines, run_lines});         // (both offsets move together: they start equal)
-        for (int j = 0; j < 2; ++j) { ofs[j] -= run_lines; if (ofs[j] == 0) ofs[j] = w->lines; }
-        run_ofs += run_lines;
-        left -= run_lines;
-    }
-    // Only the first and the last run can be shorter than the ring; every run between them rewrites all of it.  So whatever came before the run
-    // in front of the last one is overwritten: the last two runs decide every row that changes, the later one where they overlap.
+    const WfUpdatePlan plan = wf_plan_update(w->ofs[0], w->lines, n);             // :139-158
     WfUpdateArgs a{};
-    a.n_runs = (int)std::min<size_t>(runs.size(), 2);
-    for (int k = 0; k < a.n_runs; ++k) a.run[k] = runs[runs.size() - (size_t)a.n_runs + (size_t)k];
+    a.run[0] = plan.run[0]; a.run[1] = plan.run[1]; a.n_runs = plan.n_runs;
     a.n_pending = n; a.pitch = w->pitch;
     for (int j = 0; j < 2; ++j) { a.ring[j] = w->ring_of(j); a.pend[j] = w->pend_of(j); }
-    const int rows = a.run[0].n + (a.n_runs > 1 ? a.run[1].n : 0), chunks = w->pitch / 16;
+    const int rows = plan.rows(), chunks = w->pitch / 16;
     const dim3 grid((unsigned)std::min((chunks + kWfThreads - 1) / kWfThreads, 64), (unsigned)std::min(rows, 65535), 2);
     WF_LAUNCH(w, KID_WF_UPDATE, wf_update, grid, 0, a);
     CSDR_HIP_TRY(hipGetLastError());
-    w->ofs[0] = ofs[0]; w->ofs[1] = ofs[1];
+    w->ofs[0] = w->ofs[1] = plan.ofs;                    // (both offsets move together: they start equal)
     w->lines_buffered = 0;
     return CSDR_OK;
 }
@@ -234,12 +210,7 @@ extern "C" int csdr_waterfall_fetch_index(csdr_waterfall *w, int half, uint8_t *
     if (!w || !w->ready || !w->tex_init) return fail(CSDR_ESTATE, "no textures yet (setup, step, update)");
     if ((half != 0 && half != 1) || !out_u8) return fail(CSDR_EINVAL, "bad argument");
     if (cap < (int64_t)w->lines * w->half) return fail(CSDR_ERANGE, "need %lld bytes", (long long)w->lines * w->half);
-    const uint8_t *src = w->ring_of(half);
-    if (w->pitch == w->half) CSDR_HIP_TRY(hipMemcpyAsync(out_u8, src, (size_t)w->lines * w->half, hipMemcpyDeviceToHost, w->st));
-    else for (int r = 0; r < w->lines; ++r)
-        CSDR_HIP_TRY(hipMemcpyAsync(out_u8 + (size_t)r * w->half, src + (size_t)r * w->pitch, (size_t)w->half, hipMemcpyDeviceToHost, w->st));
-    CSDR_HIP_TRY(hipStreamSynchronize(w->st));
-    return CSDR_OK;
+    return wf_fetch_rows(w->st, w->ring_of(half), w->lines, w->half, w->pitch, out_u8);
 }
 
 // drawPanelContents (:161-219), unscaled
@@ -270,8 +241,7 @@ extern "C" int csdr_waterfall_device_rgba(csdr_waterfall *w, const uint8_t **dev
     DeviceScope dev__(w ? w->ctx : nullptr);
     if (!w || !dev) return fail(CSDR_EINVAL, "null argument");
     if (!w->ready || w->image_pixels == 0) return fail(CSDR_ESTATE, "nothing rendered yet (csdr_waterfall_fetch_rgba)");
-    CSDR_HIP_TRY(hipEventRecord(w->ev_out, w->st));       // whatever the caller enqueues on the boundary stream next reads the finished picture
-    CSDR_HIP_TRY(hipStreamWaitEvent(w->ctx->stream, w->ev_out, 0));
+    if (int rc = wf_hand_over(w->ev_out, w->st, w->ctx->stream)) return rc;
     *dev = reinterpret_cast<const uint8_t *>(w->image.p);
     return CSDR_OK;
 }
@@ -293,44 +263,35 @@ extern "C" int csdr_design_view_rows(int lines, int height, int mode, csdr_view_
 
 constexpr int kWfPeakSlots = 1024;           // 16 KB of LDS for a tile's texel span: nine workgroups to a compute unit
 
-// the tap tables of (width, height, mode) on the device; for PEAK also the tiling: as many pixels to a workgroup (up to one per work-item) as keep
-// the tile's span, widened to 16-byte chunks, inside the slots -- a single pixel wider than that is a tile of its own and is folded by the kernel
+// the tap tables of (width, height, mode) on the device; for PEAK, when they are rebuilt, also the tiling: as many pixels to a workgroup (up to one
+// per work-item) as keep the tile's span, widened to 16-byte chunks, inside the slots -- a single pixel wider than that is a tile of its own and is
+// folded by the kernel
 static int wf_view_tables(csdr_waterfall *w, int width, int height, int mode) {
-    if (w->taps_mode == mode && w->taps_w == width && w->taps_h == height) return CSDR_OK;
-    std::vector<csdr_view_tap> t((size_t)width + (size_t)height);
-    if (int rc = csdr_design_view_columns(w->fft_size, width, mode, t.data())) return rc;
-    if (int rc = csdr_design_view_rows(w->lines, height, mode, t.data() + width)) return rc;
-    int tile[2] = {0, 0}, slots = 1;
-    if (mode == CSDR_WF_VIEW_PEAK) {
-        const int n0 = width / 2;
-        for (int h = 0; h < 2; ++h) {
-            const int64_t nh = h ? width - n0 : n0;
-            tile[h] = (int)std::max<int64_t>(1, std::min<int64_t>(kWfThreads, ((int64_t)kWfPeakSlots * 16 - 32) * nh / w->half));
-            const csdr_view_tap *c = t.data() + (h ? n0 : 0);
-            for (int64_t k0 = 0; k0 < nh; k0 += tile[h]) {
-                const csdr_view_tap &a = c[k0], &b = c[std::min<int64_t>(k0 + tile[h], nh) - 1];
-                const int chunks = (b.first + b.count + 15) / 16 - a.first / 16;
-                if (chunks > kWfPeakSlots && tile[h] > 1) return fail(CSDR_EINVAL, "view tiling: %d chunks for %d pixels", chunks, tile[h]);
-                slots = std::max(slots, std::min(chunks, kWfPeakSlots));
+    return w->taps.ensure(w->st, w->fft_size, w->lines, width, height, mode, [&](const csdr_view_tap *t) {
+        int tile[2] = {0, 0}, slots = 1;
+        if (mode == CSDR_WF_VIEW_PEAK) {
+            const int n0 = width / 2;
+            for (int h = 0; h < 2; ++h) {
+                const int64_t nh = h ? width - n0 : n0;
+                tile[h] = (int)std::max<int64_t>(1, std::min<int64_t>(kWfThreads, ((int64_t)kWfPeakSlots * 16 - 32) * nh / w->half));
+                const csdr_view_tap *c = t + (h ? n0 : 0);
+                for (int64_t k0 = 0; k0 < nh; k0 += tile[h]) {
+                    const csdr_view_tap &a = c[k0], &b = c[std::min<int64_t>(k0 + tile[h], nh) - 1];
+                    const int chunks = (b.first + b.count + 15) / 16 - a.first / 16;
+                    if (chunks > kWfPeakSlots && tile[h] > 1) return fail(CSDR_EINVAL, "view tiling: %d chunks for %d pixels", chunks, tile[h]);
+                    slots = std::max(slots, std::min(chunks, kWfPeakSlots));
+                }
             }
         }
-    }
-    CSDR_HIP_TRY(hipStreamSynchronize(w->st));           // a kernel or an upload may still read what is replaced
-    if (int rc = w->taps.reserve(t.size())) { w->taps_mode = -1; return rc; }
-    w->taps_host.swap(t);
-    w->taps_mode = -1;
-    CSDR_HIP_TRY(hipMemcpyAsync(w->taps.p, w->taps_host.data(), w->taps_host.size() * sizeof(csdr_view_tap), hipMemcpyHostToDevice, w->st));
-    w->taps_w = width; w->taps_h = height; w->taps_mode = mode;
-    w->peak_tile[0] = tile[0]; w->peak_tile[1] = tile[1]; w->peak_slots = slots;
-    return CSDR_OK;
+        w->peak_tile[0] = tile[0]; w->peak_tile[1] = tile[1]; w->peak_slots = slots;      // (read only while `taps` holds these tables)
+        return (int)CSDR_OK;
+    });
 }
 
 extern "C" int csdr_waterfall_render_view(csdr_waterfall *w, int width, int height, int mode, uint8_t *out_u8, int64_t cap) {
     DeviceScope dev__(w ? w->ctx : nullptr);
     if (!w || !w->ready || !w->tex_init) return fail(CSDR_ESTATE, "no textures yet (setup, step, update)");         // :162-164
-    if (w->fft_size < 4 || width < 2 || width > design::kViewMaxSide || height < 1 || height > design::kViewMaxSide ||
-        (mode != CSDR_WF_VIEW_LINEAR && mode != CSDR_WF_VIEW_PEAK))
-        return fail(CSDR_EINVAL, "view %d x %d, mode %d of fft_size %d (fft_size >= 4, width 2 .. 16384, height 1 .. 16384)", width, height, mode, w->fft_size);
+    if (int rc = wf_check_view(w->fft_size, width, height, mode)) return rc;
     const int64_t pixels = (int64_t)width * height;
     if (out_u8 && cap < 4 * pixels) return fail(CSDR_ERANGE, "need %lld bytes", (long long)(4 * pixels));
     if (int rc = wf_view_tables(w, width, height, mode)) return rc;
@@ -341,7 +302,7 @@ extern "C" int csdr_waterfall_render_view(csdr_waterfall *w, int width, int heig
     if (int rc = w->view.reserve((size_t)pixels)) return rc;
     WfViewArgs a{};
     a.ring[0] = w->ring_of(0); a.ring[1] = w->ring_of(1); a.table = w->table.p;
-    a.cols = w->taps.p; a.rows = w->taps.p + width; a.out = w->view.p;
+    a.cols = w->taps.dev.p; a.rows = w->taps.dev.p + width; a.out = w->view.p;
     a.width = width; a.height = height; a.pitch = w->pitch; a.lines = w->lines; a.ofs = w->ofs[0];
     if (mode == CSDR_WF_VIEW_LINEAR) {
         const int groups = (width + 3) / 4;
@@ -367,8 +328,7 @@ extern "C" int csdr_waterfall_device_view(csdr_waterfall *w, const uint8_t **dev
     DeviceScope dev__(w ? w->ctx : nullptr);
     if (!w || !dev) return fail(CSDR_EINVAL, "null argument");
     if (!w->ready || w->view_w == 0) return fail(CSDR_ESTATE, "nothing rendered yet (csdr_waterfall_render_view)");
-    CSDR_HIP_TRY(hipEventRecord(w->ev_out, w->st));       // whatever the caller enqueues on the boundary stream next reads the finished view
-    CSDR_HIP_TRY(hipStreamWaitEvent(w->ctx->stream, w->ev_out, 0));
+    if (int rc = wf_hand_over(w->ev_out, w->st, w->ctx->stream)) return rc;
     *dev = reinterpret_cast<const uint8_t *>(w->view.p);
     if (width) *width = w->view_w;
     if (height) *height = w->view_h;

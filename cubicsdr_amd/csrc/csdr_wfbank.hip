@@ -12,6 +12,7 @@
 #define CSDR_TU_WFBANK 1     // this unit is the home of its kernels (kernels_wfbank.hpp)
 #include "csdr_objects.hpp"
 #include "kernels_wfbank.hpp"
+#include "waterfall_host.hpp"
 
 using namespace csdr;
 
@@ -52,15 +53,9 @@ struct csdr_wfbank {
     DevBuf<float> points;                              // [max_slots][2 copies][fp]
     DevBuf<uint8_t> pend, ring;                        // lineBuffer[2] per slot: [max_slots][2][max_pending][pitch]; the textures: [max_slots][2][lines][pitch]
     DevBuf<uint32_t> table, view;                      // the 256-entry RGBA8 table; the last rendered atlas
-    DevBuf<csdr_view_tap> taps;                        // [width] columns, then [height] rows: one pair of tables for all slots
-    std::vector<csdr_view_tap> taps_host;              // (the upload's source: stays until the next rebuild)
-    int taps_w = 0, taps_h = 0, taps_mode = -1;        // what `taps` was designed for; taps_mode -1: nothing
+    WfTapCache taps;                                   // one pair of tables for all slots: they share fft_size and lines
     int view_w = 0, view_h = 0;                        // the last rendered atlas in pixels; 0: none
-    DevBuf<char> plan;                                 // the records of the call being run (and the staged host lines of a step behind them)
-    PinBuf<char> plan_h[kWbStage];
-    hipEvent_t plan_ev[kWbStage] = {nullptr, nullptr};
-    bool plan_used[kWbStage] = {false, false};
-    int plan_next = 0;
+    StageRing<kWbStage> plan;                          // the records of the call being run (and the staged host lines of a step behind them)
     // scratch of a call's planning
     std::vector<WbPlan> work;
     std::vector<int> touched;
@@ -75,30 +70,6 @@ struct csdr_wfbank {
 #define WFB_LAUNCH(w_, kid_, kern_, grid_, block_, lds_, ...) \
     do { ProfScope ps__((w_)->ctx, (kid_), (w_)->st); hipLaunchKernelGGL(kern_, grid_, dim3((unsigned)(block_)), lds_, (w_)->st, __VA_ARGS__); } while (0)
 
-static int wb_upload_table(csdr_wfbank *w, const uint32_t *t) {
-    CSDR_HIP_TRY(hipMemcpyAsync(w->table.p, t, 256 * sizeof(uint32_t), hipMemcpyHostToDevice, w->st));
-    CSDR_HIP_TRY(hipStreamSynchronize(w->st));          // (t is the caller's stack)
-    return CSDR_OK;
-}
-
-// The next page-locked staging set with room for `bytes`, and the device buffer behind it.  The one host wait of a call: for the upload that last
-// used this set, kWbStage calls ago.
-static int wb_stage_begin(csdr_wfbank *w, size_t bytes, int *k_out) {
-    const int k = w->plan_next;
-    w->plan_next = (w->plan_next + 1) % kWbStage;
-    if (w->plan_used[k]) { CSDR_HIP_TRY(hipEventSynchronize(w->plan_ev[k])); w->plan_used[k] = false; }
-    if (int rc = w->plan_h[k].reserve(bytes)) return rc;
-    if (bytes > w->plan.cap) CSDR_HIP_TRY(hipStreamSynchronize(w->st));          // (a kernel may still read the buffer being replaced)
-    if (int rc = w->plan.reserve(bytes)) return rc;
-    *k_out = k;
-    return CSDR_OK;
-}
-static int wb_stage_upload(csdr_wfbank *w, int k, size_t bytes) {
-    CSDR_HIP_TRY(hipMemcpyAsync(w->plan.p, w->plan_h[k].p, bytes, hipMemcpyHostToDevice, w->st));
-    CSDR_HIP_TRY(hipEventRecord(w->plan_ev[k], w->st));
-    w->plan_used[k] = true;
-    return CSDR_OK;
-}
 // the workgroup for `items` work-items of a row: whole waves, 256 work-items at most
 static int wb_block(int items) { return std::min(kWfThreads, (items + 63) / 64 * 64); }
 
@@ -110,11 +81,9 @@ extern "C" int csdr_wfbank_create(csdr_ctx *ctx, csdr_wfbank **out) {
     CSDR_HIP_TRY(hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking));
     CSDR_HIP_TRY(hipEventCreateWithFlags(&w->ev_in, hipEventDisableTiming));
     CSDR_HIP_TRY(hipEventCreateWithFlags(&w->ev_out, hipEventDisableTiming));
-    for (int k = 0; k < kWbStage; ++k) CSDR_HIP_TRY(hipEventCreateWithFlags(&w->plan_ev[k], hipEventDisableTiming));
+    if (int rc = w->plan.create()) return rc;
     if (int rc = w->table.reserve(256)) return rc;
-    uint32_t grey[256];                                  // before any csdr_wfbank_set_gradient: i -> (i, i, i, 255)
-    for (uint32_t i = 0; i < 256; ++i) grey[i] = i | (i << 8) | (i << 16) | 0xff000000u;
-    if (int rc = wb_upload_table(w.get(), grey)) return rc;
+    if (int rc = wf_upload_grey_table(w->st, w->table.p)) return rc;        // before any csdr_wfbank_set_gradient
     *out = w.release();
     return CSDR_OK;
 }
@@ -125,8 +94,8 @@ extern "C" void csdr_wfbank_destroy(csdr_wfbank *w) {
     if (w->st) { (void)hipStreamSynchronize(w->st); (void)hipStreamDestroy(w->st); }
     if (w->ev_in) (void)hipEventDestroy(w->ev_in);
     if (w->ev_out) (void)hipEventDestroy(w->ev_out);
-    for (int k = 0; k < kWbStage; ++k) { if (w->plan_ev[k]) (void)hipEventDestroy(w->plan_ev[k]); w->plan_h[k].release(); }
-    w->points.release(); w->pend.release(); w->ring.release(); w->table.release(); w->view.release(); w->taps.release(); w->plan.release();
+    w->plan.destroy();
+    w->points.release(); w->pend.release(); w->ring.release(); w->table.release(); w->view.release(); w->taps.dev.release();
     delete w;
 }
 
@@ -173,7 +142,7 @@ extern "C" int csdr_wfbank_setup(csdr_wfbank *w, int fft_size, int lines, int ma
     }
     w->work.assign((size_t)max_slots, WbPlan());
     w->touched.clear();
-    w->taps_mode = -1; w->view_w = w->view_h = 0;
+    w->taps.forget(); w->view_w = w->view_h = 0;
     w->ready = true;
     return CSDR_OK;
 }
@@ -184,7 +153,7 @@ extern "C" int csdr_wfbank_set_gradient(csdr_wfbank *w, const float *rgb_stops, 
     if (!w) return fail(CSDR_EINVAL, "waterfall bank is null");
     uint32_t t[256];
     if (!design::gradient_rgba8(rgb_stops, n_colors, t)) return fail(CSDR_EINVAL, "gradient: %d stops (2 .. 257, no null pointer)", n_colors);
-    return wb_upload_table(w, t);
+    return wf_upload_table(w->st, w->table.p, t);
 }
 
 extern "C" int csdr_wfbank_reset_slot(csdr_wfbank *w, int slot) {
@@ -202,11 +171,7 @@ extern "C" int csdr_wfbank_reset_slot(csdr_wfbank *w, int slot) {
 static int wb_step(csdr_wfbank *w, const csdr_wfbank_item *items, int n_items, int *taken, bool from_boundary) {
     if (taken) for (int i = 0; i < n_items; ++i) taken[i] = 0;
     const int F = w->fft_size;
-    auto good = [F](const csdr_wfbank_item &it) {
-        // 2 fft_size floats: the (x, y) pairs of SpectrumVisualData (:40-45); fft_size floats: as they stand (:47); anything else leaves the
-        // points alone (WaterfallCanvas.cpp:106-109) and the step repeats them
-        return it.points && (it.n_floats_per_line == 2 * F || it.n_floats_per_line == F);
-    };
+    auto good = [F](const csdr_wfbank_item &it) { return wf_good_line(it.points, it.n_floats_per_line, F); };       // (else the step repeats the points)
     auto forget = [w]() { for (int s : w->touched) w->work[(size_t)s] = WbPlan(); w->touched.clear(); };
     // ---- count: a refused call leaves every slot as it was
     size_t n_jobs = 0, host_floats = 0;
@@ -241,15 +206,14 @@ static int wb_step(csdr_wfbank *w, const csdr_wfbank_item *items, int n_items, i
     for (int s : w->touched) w->slots[(size_t)s].buffer_init = true;             // :54-58
     if (n_jobs == 0) { forget(); return CSDR_OK; }       // steps without points on slots without textures: nothing to quantise, nothing to keep
     const size_t lines_at = n_jobs * sizeof(WfbJob), bytes = lines_at + host_floats * sizeof(float);
-    int k = 0;
-    if (int rc = wb_stage_begin(w, bytes, &k)) { forget(); return rc; }
+    if (int rc = w->plan.begin(w->st, bytes)) { forget(); return rc; }
     if (any_dev && from_boundary) {
         CSDR_HIP_TRY(hipEventRecord(w->ev_in, w->ctx->stream));                  // the caller produced them on the boundary stream
         CSDR_HIP_TRY(hipStreamWaitEvent(w->st, w->ev_in, 0));
     }
-    WfbJob *jobs = reinterpret_cast<WfbJob *>(w->plan_h[k].p);
-    float *stage_h = reinterpret_cast<float *>(w->plan_h[k].p + lines_at);
-    const float *stage_d = reinterpret_cast<const float *>(w->plan.p + lines_at);
+    WfbJob *jobs = reinterpret_cast<WfbJob *>(w->plan.host());
+    float *stage_h = reinterpret_cast<float *>(w->plan.host() + lines_at);
+    const float *stage_d = reinterpret_cast<const float *>(w->plan.device() + lines_at);
     size_t nj = 0, at = 0;
     const bool wide_ok = w->half % 16 == 0;
     auto line_flags = [wide_ok](const float *dev, bool pair) { return (pair ? kWfbPair : 0) | (wide_ok && ((uintptr_t)dev & 15) == 0 ? kWfbWide : 0); };
@@ -265,7 +229,7 @@ static int wb_step(csdr_wfbank *w, const csdr_wfbank_item *items, int n_items, i
         const WbSlot &sl = w->slots[(size_t)it.slot];
         WbPlan &p = w->work[(size_t)it.slot];
         if (!sl.tex_init) continue;
-        const bool ok = good(it), pair = it.n_floats_per_line == 2 * F;
+        const bool ok = good(it), pair = wf_line_is_pairs(it.n_floats_per_line, F);
         for (int l = 0; l < it.n_lines; ++l) {
             WfbJob jb{};
             jb.slot = it.slot; jb.row = sl.lines_buffered + p.added++;
@@ -287,7 +251,7 @@ static int wb_step(csdr_wfbank *w, const csdr_wfbank_item *items, int n_items, i
             WfbJob jb{};
             jb.slot = s; jb.row = -1;
             jb.src = p.drop_dev ? p.drop : stage_line(p.drop, p.drop_nf);
-            jb.flags = line_flags(jb.src, p.drop_nf == 2 * F);
+            jb.flags = line_flags(jb.src, wf_line_is_pairs(p.drop_nf, F));
             p.keep_job = (int)nj;
             jobs[nj++] = jb;
         }
@@ -299,9 +263,9 @@ static int wb_step(csdr_wfbank *w, const csdr_wfbank_item *items, int n_items, i
         sl.lines_buffered += p.added;
     }
     forget();
-    if (int rc = wb_stage_upload(w, k, lines_at + at * sizeof(float))) return rc;
+    if (int rc = w->plan.uploaded(w->st, lines_at + at * sizeof(float))) return rc;
     WfbQuantArgs a{};
-    a.jobs = reinterpret_cast<const WfbJob *>(w->plan.p); a.n_jobs = (int)nj;
+    a.jobs = reinterpret_cast<const WfbJob *>(w->plan.device()); a.n_jobs = (int)nj;
     a.half = w->half; a.pitch = w->pitch; a.pend = w->pend.p; a.pend_half = w->pend_half();
     const int items_x = (w->half + kWfChunk - 1) / kWfChunk, block = wb_block(items_x);
     const dim3 grid((unsigned)((items_x + block - 1) / block), (unsigned)std::min<size_t>(nj, 65535), 2);
@@ -358,9 +322,8 @@ extern "C" int csdr_wfbank_update(csdr_wfbank *w) {
     if (!w || !w->ready) return fail(CSDR_ESTATE, "waterfall bank not set up");
     size_t n_upd = 0;
     for (const WbSlot &s : w->slots) if (s.buffer_init && s.lines_buffered > 0) ++n_upd;
-    int k = 0;
-    if (n_upd) if (int rc = wb_stage_begin(w, n_upd * sizeof(WfbUpdate), &k)) return rc;
-    WfbUpdate *upd = n_upd ? reinterpret_cast<WfbUpdate *>(w->plan_h[k].p) : nullptr;
+    if (n_upd) if (int rc = w->plan.begin(w->st, n_upd * sizeof(WfbUpdate))) return rc;
+    WfbUpdate *upd = n_upd ? reinterpret_cast<WfbUpdate *>(w->plan.host()) : nullptr;
     size_t nu = 0;
     int rows_max = 0, fill0 = -1;                        // fill0: first slot of a run of neighbours whose textures are being created
     const size_t slot_bytes = 2 * (size_t)w->ring_half();
@@ -376,32 +339,19 @@ extern "C" int csdr_wfbank_update(csdr_wfbank *w) {
         if (create) { s->ofs = w->lines - 1; s->tex_init = true; }
         const int n = s->lines_buffered;
         if (n == 0) continue;
-        // :139-158 literally: runs of min(lines_buffered, waterfall_ofs[0]) rows at [ofs - run, ofs), an offset that reaches 0 becomes waterfall_lines.
-        // Only the first and the last run can be shorter than the ring, so the last two runs decide every row that changes (csdr_waterfall_update)
+        const WfUpdatePlan plan = wf_plan_update(s->ofs, w->lines, n);           // :139-158
         WfbUpdate u{};
-        u.slot = si; u.n_pending = n;
-        int run_ofs = 0, left = n, ofs = s->ofs;
-        while (left) {
-            const int run_lines = std::min(left, ofs);
-            u.run[0] = u.run[1];
-            u.run[1] = WfRun{run_ofs, ofs - run_lines, run_lines};
-            ++u.n_runs;
-            ofs -= run_lines;
-            if (ofs == 0) ofs = w->lines;
-            run_ofs += run_lines;
-            left -= run_lines;
-        }
-        if (u.n_runs == 1) { u.run[0] = u.run[1]; u.run[1] = WfRun{0, 0, 0}; }
-        u.n_runs = std::min(u.n_runs, 2);
-        rows_max = std::max(rows_max, u.run[0].n + (u.n_runs > 1 ? u.run[1].n : 0));
+        u.slot = si; u.n_pending = n; u.n_runs = plan.n_runs;
+        u.run[0] = plan.run[0]; u.run[1] = plan.run[1];
+        rows_max = std::max(rows_max, plan.rows());
         upd[nu++] = u;
-        s->ofs = ofs;
+        s->ofs = plan.ofs;
         s->lines_buffered = 0;
     }
     if (nu == 0) return CSDR_OK;
-    if (int rc = wb_stage_upload(w, k, nu * sizeof(WfbUpdate))) return rc;
+    if (int rc = w->plan.uploaded(w->st, nu * sizeof(WfbUpdate))) return rc;
     WfbUpdateArgs a{};
-    a.upd = reinterpret_cast<const WfbUpdate *>(w->plan.p);
+    a.upd = reinterpret_cast<const WfbUpdate *>(w->plan.device());
     a.pitch = w->pitch; a.ring = w->ring.p; a.pend = w->pend.p; a.ring_half = w->ring_half(); a.pend_half = w->pend_half();
     const int chunks = w->pitch / 16, block = wb_block(chunks);
     const dim3 grid((unsigned)((chunks + block - 1) / block), (unsigned)std::min(rows_max, 65535), (unsigned)(2 * nu));
@@ -423,37 +373,14 @@ extern "C" int csdr_wfbank_fetch_index(csdr_wfbank *w, int slot, int half, uint8
     if (slot < 0 || slot >= w->max_slots || (half != 0 && half != 1) || !out_u8) return fail(CSDR_EINVAL, "bad argument");
     if (!w->slots[(size_t)slot].tex_init) return fail(CSDR_ESTATE, "slot %d: no textures yet (setup, step, update)", slot);
     if (cap < (int64_t)w->lines * w->half) return fail(CSDR_ERANGE, "need %lld bytes", (long long)w->lines * w->half);
-    const uint8_t *src = w->ring_of(slot, half);
-    if (w->pitch == w->half) CSDR_HIP_TRY(hipMemcpyAsync(out_u8, src, (size_t)w->lines * w->half, hipMemcpyDeviceToHost, w->st));
-    else for (int r = 0; r < w->lines; ++r)
-        CSDR_HIP_TRY(hipMemcpyAsync(out_u8 + (size_t)r * w->half, src + (size_t)r * w->pitch, (size_t)w->half, hipMemcpyDeviceToHost, w->st));
-    CSDR_HIP_TRY(hipStreamSynchronize(w->st));
-    return CSDR_OK;
-}
-
-// the tap tables of (width, height, mode) on the device: one pair for all slots -- they share fft_size and lines, and the taps do not depend on
-// the offset -- rebuilt only when one of the three changes
-static int wb_view_tables(csdr_wfbank *w, int width, int height, int mode) {
-    if (w->taps_mode == mode && w->taps_w == width && w->taps_h == height) return CSDR_OK;
-    std::vector<csdr_view_tap> t((size_t)width + (size_t)height);
-    if (int rc = csdr_design_view_columns(w->fft_size, width, mode, t.data())) return rc;
-    if (int rc = csdr_design_view_rows(w->lines, height, mode, t.data() + width)) return rc;
-    CSDR_HIP_TRY(hipStreamSynchronize(w->st));           // a kernel or an upload may still read what is replaced
-    w->taps_mode = -1;
-    if (int rc = w->taps.reserve(t.size())) return rc;
-    w->taps_host.swap(t);
-    CSDR_HIP_TRY(hipMemcpyAsync(w->taps.p, w->taps_host.data(), w->taps_host.size() * sizeof(csdr_view_tap), hipMemcpyHostToDevice, w->st));
-    w->taps_w = width; w->taps_h = height; w->taps_mode = mode;
-    return CSDR_OK;
+    return wf_fetch_rows(w->st, w->ring_of(slot, half), w->lines, w->half, w->pitch, out_u8);
 }
 
 // drawPanelContents (:161-219) of every listed slot, scaled to width x height, as one atlas
 extern "C" int csdr_wfbank_render(csdr_wfbank *w, const int *slots, int n_slots, int width, int height, int mode, int atlas_cols, uint8_t *out_u8, int64_t cap) {
     DeviceScope dev__(w ? w->ctx : nullptr);
     if (!w || !w->ready) return fail(CSDR_ESTATE, "waterfall bank not set up");
-    if (w->fft_size < 4 || width < 2 || width > design::kViewMaxSide || height < 1 || height > design::kViewMaxSide ||
-        (mode != CSDR_WF_VIEW_LINEAR && mode != CSDR_WF_VIEW_PEAK))
-        return fail(CSDR_EINVAL, "view %d x %d, mode %d of fft_size %d (fft_size >= 4, width 2 .. 16384, height 1 .. 16384)", width, height, mode, w->fft_size);
+    if (int rc = wf_check_view(w->fft_size, width, height, mode)) return rc;
     if (n_slots < 1 || n_slots > (1 << 20)) return fail(CSDR_EINVAL, "n_slots %d: 1 .. 2^20", n_slots);
     if (atlas_cols < 1 || atlas_cols > n_slots) return fail(CSDR_EINVAL, "atlas_cols %d: 1 .. n_slots (%d)", atlas_cols, n_slots);
     if (slots) for (int i = 0; i < n_slots; ++i) if (slots[i] < 0 || slots[i] >= w->max_slots) return fail(CSDR_EINVAL, "entry %d: slot %d of %d", i, slots[i], w->max_slots);
@@ -464,24 +391,23 @@ extern "C" int csdr_wfbank_render(csdr_wfbank *w, const int *slots, int n_slots,
     const int groups = (width + 3) / 4, per_tile = (int)(((int64_t)groups * height + kWfThreads - 1) / kWfThreads);
     if (pic_w > 0x7fffffff || pic_h > 0x7fffffff || n_tiles * per_tile > 0x7fffffff) return fail(CSDR_EINVAL, "an atlas of %lld x %lld pixels", (long long)pic_w, (long long)pic_h);
     if (out_u8 && cap < 4 * pixels) return fail(CSDR_ERANGE, "need %lld bytes", (long long)(4 * pixels));
-    if (int rc = wb_view_tables(w, width, height, mode)) return rc;
+    if (int rc = w->taps.ensure(w->st, w->fft_size, w->lines, width, height, mode)) return rc;
     if ((size_t)pixels > w->view.cap) {
         CSDR_HIP_TRY(hipStreamSynchronize(w->st));
         w->view_w = w->view_h = 0;                       // (the buffer csdr_wfbank_device_view handed out goes away)
     }
     if (int rc = w->view.reserve((size_t)pixels)) return rc;
-    int k = 0;
-    if (int rc = wb_stage_begin(w, (size_t)n_tiles * sizeof(WfbTile), &k)) return rc;
-    WfbTile *tiles = reinterpret_cast<WfbTile *>(w->plan_h[k].p);
+    if (int rc = w->plan.begin(w->st, (size_t)n_tiles * sizeof(WfbTile))) return rc;
+    WfbTile *tiles = reinterpret_cast<WfbTile *>(w->plan.host());
     for (int64_t t = 0; t < n_tiles; ++t) {
         const int s = t < n_slots ? (slots ? slots[t] : (int)t) : -1;
         tiles[t] = WfbTile{std::max(s, 0), s >= 0 && w->slots[(size_t)s].tex_init ? w->slots[(size_t)s].ofs : -1};       // :162-164 per slot: nothing is drawn
     }
-    if (int rc = wb_stage_upload(w, k, (size_t)n_tiles * sizeof(WfbTile))) return rc;
+    if (int rc = w->plan.uploaded(w->st, (size_t)n_tiles * sizeof(WfbTile))) return rc;
     WfbViewArgs a{};
-    a.tiles = reinterpret_cast<const WfbTile *>(w->plan.p);
+    a.tiles = reinterpret_cast<const WfbTile *>(w->plan.device());
     a.ring = w->ring.p; a.ring_half = w->ring_half(); a.table = w->table.p;
-    a.cols = w->taps.p; a.rows = w->taps.p + width; a.out = w->view.p;
+    a.cols = w->taps.dev.p; a.rows = w->taps.dev.p + width; a.out = w->view.p;
     a.width = width; a.height = height; a.pitch = w->pitch; a.lines = w->lines; a.atlas_cols = atlas_cols;
     if (mode == CSDR_WF_VIEW_LINEAR) {
         a.groups = groups; a.per_tile = per_tile;
@@ -506,8 +432,7 @@ extern "C" int csdr_wfbank_device_view(csdr_wfbank *w, const uint8_t **dev, int 
     DeviceScope dev__(w ? w->ctx : nullptr);
     if (!w || !dev) return fail(CSDR_EINVAL, "null argument");
     if (!w->ready || w->view_w == 0) return fail(CSDR_ESTATE, "nothing rendered yet (csdr_wfbank_render)");
-    CSDR_HIP_TRY(hipEventRecord(w->ev_out, w->st));       // whatever the caller enqueues on the boundary stream next reads the finished atlas
-    CSDR_HIP_TRY(hipStreamWaitEvent(w->ctx->stream, w->ev_out, 0));
+    if (int rc = wf_hand_over(w->ev_out, w->st, w->ctx->stream)) return rc;
     *dev = reinterpret_cast<const uint8_t *>(w->view.p);
     if (pic_width) *pic_width = w->view_w;
     if (pic_height) *pic_height = w->view_h;

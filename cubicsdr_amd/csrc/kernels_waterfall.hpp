@@ -11,6 +11,11 @@
 // table (wave-uniform tables live in LDS in this project), no scratch.  The pending lines and both ring textures are kept with a row pitch that is
 // a multiple of 16 bytes, so every row starts on a 16-byte boundary whatever fft_size / 2 is; a row's last fft_size / 2 % 16 bytes are written one
 // by one.  The two viewport kernels read tap tables the host designs (design.hpp: view_columns / view_rows) -- no coordinate arithmetic on the device.
+// A kernel is its own "which line, which row, which pixel" arithmetic around a body, and the bodies are __device__ __forceinline__ functions that
+// kernels_wfbank.hpp (N panels per launch) calls too: wf_quantize_chunk, wf_stage_table, wf_store4, wf_linear4, wf_footprint_max, wf_scan_max
+// (the row copy of wf_update / wfb_update and the pixel store of wf_rgba stay separate copies; wf_rgba's store and wf_store4 are one
+// rule in two places: a change to the store-alignment rule goes to both).  None of the shared ones knows its caller; what differs between a
+// panel and a bank arrives as data (an empty span, a null pointer, a base).
 // Home unit: csdr_waterfall.hip.
 #pragma once
 #include "common.hpp"
@@ -76,6 +81,57 @@ struct WfQuantArgs {
     HideDcSpan dc;                           // csdr_waterfall_step_spec with hideDC: the span to gather around
 };
 
+// One 16-point chunk of one line, the body of wf_quantize and wfb_quantize: points [p0, p0 + cnt) of `line` in either layout, gathered around `dc`
+// (an empty span folds the gather away), packed to index bytes, stored to `row` (store false: a dropped step, :60-62) and as they are to
+// keep[p0 ...] (`keep`: the panel's `points`; nullptr: not the line they receive).  wide_load / wide_keep: the chunk is whole and the line / `keep`
+// can be accessed 16 bytes at a time.  `row` is 16-byte aligned: the pitch and the chunk's first byte are multiples of 16.  With store false
+// `row` is not looked at and may be any address, one outside the pending rows included (the callers form it from the line's row number, which is
+// -1 for a dropped step of the bank): it is only ever dereferenced under `store`.
+__device__ __forceinline__ void wf_quantize_chunk(const float *line, bool pair, const HideDcSpan &dc, int p0, int cnt, bool wide_load, bool wide_keep,
+                                                  bool store, uint8_t *row, float *keep) {
+    float v[kWfChunk];
+    if (wide_load) {
+        if (pair) {
+            const float4 *s = reinterpret_cast<const float4 *>(line + 2 * (int64_t)p0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { float4 t = s[k]; pin_loaded(t); v[2 * k] = t.y; v[2 * k + 1] = t.w; }      // (pinned: whole 16-byte loads, not two 4-byte ones)
+        } else {
+            const float4 *s = reinterpret_cast<const float4 *>(line + p0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const float4 t = s[k]; v[4 * k] = t.x; v[4 * k + 1] = t.y; v[4 * k + 2] = t.z; v[4 * k + 3] = t.w; }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kWfChunk; ++k) {
+            const int p = hide_dc_source(dc, p0 + k);
+            v[k] = k < cnt ? line[pair ? 2 * (int64_t)p + 1 : (int64_t)p] : 0.0f;
+        }
+    }
+    if (store) {
+        unsigned w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) w[q] = wf_index(v[4 * q]) | (wf_index(v[4 * q + 1]) << 8) | (wf_index(v[4 * q + 2]) << 16) | (wf_index(v[4 * q + 3]) << 24);
+        if (cnt == kWfChunk) *reinterpret_cast<int4 *>(row) = make_int4((int)w[0], (int)w[1], (int)w[2], (int)w[3]);
+        else {
+#pragma unroll
+            for (int k = 0; k < kWfChunk; ++k) if (k < cnt) row[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+        }
+    }
+    if (keep) {
+        float *kp = keep + p0;
+        if (wide_keep) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {        // (one vector value each: as four floats the last is merged with the last store below and the wide store split into 12 + 4 bytes)
+                const csdr_f32x4 t = {v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]};
+                reinterpret_cast<csdr_f32x4 *>(kp)[k] = t;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kWfChunk; ++k) if (k < cnt) kp[k] = v[k];
+        }
+    }
+}
+
 // grid (chunks of a half / 256, lines, 2 halves)
 CSDR_KERNEL_WF __launch_bounds__(kWfThreads) void wf_quantize(WfQuantArgs a) {
     const int j = (int)blockIdx.z;
@@ -84,48 +140,10 @@ CSDR_KERNEL_WF __launch_bounds__(kWfThreads) void wf_quantize(WfQuantArgs a) {
     const int cnt = min(kWfChunk, a.half - i0);
     const int p0 = j * a.half + i0;                                   // byte i of half j comes from point j * half + i (:65-67)
     const bool in_dc = p0 < a.dc.end && p0 + kWfChunk > a.dc.start;   // the hideDC span is a handful of points: the items that meet it go point by point
-    for (int l = (int)blockIdx.y; l < a.n_lines; l += (int)gridDim.y) {
-        const float *line = a.src + (int64_t)l * a.line_stride;
-        float v[kWfChunk];
-        if (a.wide && cnt == kWfChunk && !in_dc) {
-            if (a.pair) {
-                const float4 *s = reinterpret_cast<const float4 *>(line + 2 * (int64_t)p0);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { float4 t = s[k]; pin_loaded(t); v[2 * k] = t.y; v[2 * k + 1] = t.w; }      // (pinned: whole 16-byte loads, not two 4-byte ones)
-            } else {
-                const float4 *s = reinterpret_cast<const float4 *>(line + p0);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { const float4 t = s[k]; v[4 * k] = t.x; v[4 * k + 1] = t.y; v[4 * k + 2] = t.z; v[4 * k + 3] = t.w; }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < kWfChunk; ++k) {
-                const int p = hide_dc_source(a.dc, p0 + k);
-                v[k] = k < cnt ? line[a.pair ? 2 * (int64_t)p + 1 : (int64_t)p] : 0.0f;
-            }
-        }
-        if (a.store) {
-            unsigned w[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) w[q] = wf_index(v[4 * q]) | (wf_index(v[4 * q + 1]) << 8) | (wf_index(v[4 * q + 2]) << 16) | (wf_index(v[4 * q + 3]) << 24);
-            uint8_t *row = a.pend[j] + (int64_t)(a.row0 + l) * a.pitch + i0;          // 16-byte aligned: pitch % 16 == 0, i0 % 16 == 0
-            if (cnt == kWfChunk) *reinterpret_cast<int4 *>(row) = make_int4((int)w[0], (int)w[1], (int)w[2], (int)w[3]);
-            else {
-#pragma unroll
-                for (int k = 0; k < kWfChunk; ++k) if (k < cnt) row[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-            }
-        }
-        if (a.keep && l == a.n_lines - 1) {
-            float *kp = a.keep + p0;
-            if (a.wide && cnt == kWfChunk) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) reinterpret_cast<float4 *>(kp)[k] = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < kWfChunk; ++k) if (k < cnt) kp[k] = v[k];
-            }
-        }
-    }
+    const bool wide = a.wide && cnt == kWfChunk;
+    for (int l = (int)blockIdx.y; l < a.n_lines; l += (int)gridDim.y)
+        wf_quantize_chunk(a.src + (int64_t)l * a.line_stride, a.pair != 0, a.dc, p0, cnt, wide && !in_dc, wide,
+                          a.store != 0, a.pend[j] + (int64_t)(a.row0 + l) * a.pitch + i0, l == a.n_lines - 1 ? a.keep : nullptr);
 }
 
 // One run of WaterfallPanel::update (:139-158): ring rows [dst, dst + n) take the rows [src, src + n) of the REVERSED pending lines (:132-137), i.e.
@@ -161,12 +179,30 @@ struct WfRgbaArgs {
     int half, pitch, lines, ofs, first_row, n_rows;
 };
 
+// The 256-entry colour table into the first 1 KB of the workgroup's LDS (every kernel that looks colours up); the caller's barrier follows.
+__device__ __forceinline__ uint32_t *wf_stage_table(char *smem, const uint32_t *table) {
+    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
+    if (threadIdx.x < 64) reinterpret_cast<int4 *>(tab)[threadIdx.x] = reinterpret_cast<const int4 *>(table)[threadIdx.x];
+    return tab;
+}
+
+// Pixels c[0 .. cnt) to out[base ...]: one 16-byte store if all four are there and the ADDRESS is on the 16-byte grid (`out` is 16-byte aligned, so
+// `base` decides: a picture row whose length is no multiple of 4 leaves the next one off the grid), else one by one.  (A loop that stays a loop:
+// unrolled, its last store is merged with the wide one, which is then split into a 12-byte and a 4-byte store.)
+__device__ __forceinline__ void wf_store4(uint32_t *out, int64_t base, int cnt, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
+    uint32_t *o = out + base;
+    if (cnt == 4 && (base & 3) == 0) *reinterpret_cast<int4 *>(o) = make_int4((int)c0, (int)c1, (int)c2, (int)c3);
+    else {
+#pragma unroll 1
+        for (int k = 0; k < cnt; ++k) o[k] = k == 0 ? c0 : (k == 1 ? c1 : (k == 2 ? c2 : c3));
+    }
+}
+
 // grid (groups of 4 pixels of a half / 256, image rows, 2 halves).  Image row r is ring row (ofs + first_row + r) mod lines (:186-213: the texture
 // coordinate runs from waterfall_ofs / lines under GL_REPEAT), half 0 then half 1.
 CSDR_KERNEL_WF __launch_bounds__(kWfThreads) void wf_rgba(WfRgbaArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
-    if (threadIdx.x < 64) reinterpret_cast<int4 *>(tab)[threadIdx.x] = reinterpret_cast<const int4 *>(a.table)[threadIdx.x];
+    const uint32_t *tab = wf_stage_table(smem, a.table);
     __syncthreads();
     const int j = (int)blockIdx.z;
     const int q = (int)blockIdx.x * kWfThreads + (int)threadIdx.x;
@@ -180,8 +216,8 @@ CSDR_KERNEL_WF __launch_bounds__(kWfThreads) void wf_rgba(WfRgbaArgs a) {
         uint32_t *o = a.out + base;
         if (cnt == 4 && (base & 3) == 0) *reinterpret_cast<int4 *>(o) = make_int4((int)c0, (int)c1, (int)c2, (int)c3);
         else {
-            // a row that does not start on a 16-byte boundary (half % 4 != 0), or its last pixels: one by one.  (A loop that stays a loop: unrolled,
-            // its last store is merged with the wide one above, which is then split into a 12-byte and a 4-byte store.)
+            // a row that does not start on a 16-byte boundary (half % 4 != 0), or its last pixels: one by one, as in wf_store4 -- whose text this is:
+            // called from here, the loop came out two pixels at a time and the kernel 1.3 us slower per 512 x 65536 picture
 #pragma unroll 1
             for (int k = 0; k < cnt; ++k) o[k] = k == 0 ? c0 : (k == 1 ? c1 : (k == 2 ? c2 : c3));
         }
@@ -215,41 +251,34 @@ __device__ __forceinline__ uint32_t wf_blend(uint32_t c00, uint32_t c10, uint32_
     return px;
 }
 
-// grid (groups of 4 pixels of a row / 256, image rows).  A gather: per pixel four byte reads (texels i0, i0 + 1 of ring rows j0, j1) and the blend.
+// LINEAR: four neighbouring pixels of one image row, the body of wf_view_linear and wfb_view_linear.  A gather: per pixel four byte reads (texels
+// first, first + 1 of the column tap, in ring rows j0, j1 of the tap's half) and the blend.  ring0 / ring1: the two halves of one ring.
+__device__ __forceinline__ void wf_linear4(const uint32_t *tab, const uint8_t *ring0, const uint8_t *ring1, int pitch, int lines, int ofs,
+                                           const csdr_view_tap (&ct)[4], const csdr_view_tap rt, uint32_t (&c)[4]) {
+    const int j0 = (int)(((int64_t)ofs + rt.first + lines) % lines), j1 = j0 + 1 == lines ? 0 : j0 + 1;                  // GL_REPEAT
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint8_t *tex = (ct[k].half ? ring1 : ring0) + ct[k].first;
+        const uint8_t *r0 = tex + (int64_t)j0 * pitch, *r1 = tex + (int64_t)j1 * pitch;
+        c[k] = wf_blend(tab[r0[0]], tab[r0[1]], tab[r1[0]], tab[r1[1]], ct[k].frac, rt.frac);
+    }
+}
+
+// grid (groups of 4 pixels of a row / 256, image rows)
 CSDR_KERNEL_WF __launch_bounds__(kWfThreads) void wf_view_linear(WfViewArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
-    if (threadIdx.x < 64) reinterpret_cast<int4 *>(tab)[threadIdx.x] = reinterpret_cast<const int4 *>(a.table)[threadIdx.x];
+    const uint32_t *tab = wf_stage_table(smem, a.table);
     __syncthreads();
     const int px0 = 4 * ((int)blockIdx.x * kWfThreads + (int)threadIdx.x);
     if (px0 >= a.width) return;
     const int cnt = min(4, a.width - px0);
-    int64_t at[4];                                                    // byte offset of texel i0 inside a ring row, in the pixel's half
-    const uint8_t *tex[4];
-    float al[4];
+    csdr_view_tap ct[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const csdr_view_tap t = a.cols[min(px0 + k, a.width - 1)];
-        tex[k] = t.half ? a.ring[1] : a.ring[0];
-        at[k] = t.first;
-        al[k] = t.frac;
-    }
+    for (int k = 0; k < 4; ++k) ct[k] = a.cols[min(px0 + k, a.width - 1)];
     for (int py = (int)blockIdx.y; py < a.height; py += (int)gridDim.y) {
-        const csdr_view_tap rt = a.rows[py];
-        const int j0 = (int)(((int64_t)a.ofs + rt.first + a.lines) % a.lines), j1 = j0 + 1 == a.lines ? 0 : j0 + 1;       // GL_REPEAT
         uint32_t c[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint8_t *r0 = tex[k] + (int64_t)j0 * a.pitch + at[k], *r1 = tex[k] + (int64_t)j1 * a.pitch + at[k];
-            c[k] = wf_blend(tab[r0[0]], tab[r0[1]], tab[r1[0]], tab[r1[1]], al[k], rt.frac);
-        }
-        const int64_t base = (int64_t)py * a.width + px0;
-        uint32_t *o = a.out + base;
-        if (cnt == 4 && (base & 3) == 0) *reinterpret_cast<int4 *>(o) = make_int4((int)c[0], (int)c[1], (int)c[2], (int)c[3]);
-        else {
-#pragma unroll 1
-            for (int k = 0; k < cnt; ++k) o[k] = k == 0 ? c[0] : (k == 1 ? c[1] : (k == 2 ? c[2] : c[3]));        // (a loop that stays a loop, as in wf_rgba)
-        }
+        wf_linear4(tab, a.ring[0], a.ring[1], a.pitch, a.lines, a.ofs, ct, a.rows[py], c);
+        wf_store4(a.out, (int64_t)py * a.width + px0, cnt, c[0], c[1], c[2], c[3]);
     }
 }
 
@@ -276,6 +305,27 @@ __device__ __forceinline__ int4 wf_keep_bytes16(int4 v, int lo, int hi) {
                      (int)((unsigned)v.z & wf_keep_bytes(lo - 8, hi - 8)), (int)((unsigned)v.w & wf_keep_bytes(lo - 12, hi - 12)));
 }
 
+// PEAK, pass 1: the element-wise max of one 16-byte chunk (`col`: its place in ring row 0) over the `count` ring rows from row0 on, wrapping at
+// `lines` (scrolled row r is ring row (ofs + r) mod lines)
+__device__ __forceinline__ int4 wf_footprint_max(const uint8_t *col, int pitch, int lines, int row0, int count) {
+    int rr = row0;
+    int4 m = *reinterpret_cast<const int4 *>(col + (int64_t)rr * pitch);
+    for (int r = 1; r < count; ++r) {
+        if (++rr == lines) rr = 0;
+        m = wf_max_u8x16(m, *reinterpret_cast<const int4 *>(col + (int64_t)rr * pitch));
+    }
+    return m;
+}
+// PEAK, pass 2: the largest of the LDS bytes [s, e) of `words`, word by word
+__device__ __forceinline__ unsigned wf_scan_max(const unsigned *words, int s, int e) {
+    unsigned best = 0;
+    for (int w = s >> 2; 4 * w < e; ++w) {
+        const unsigned x = words[w] & wf_keep_bytes(s - 4 * w, e - 4 * w);
+        best = max(best, max(max(x & 0xffu, (x >> 8) & 0xffu), max((x >> 16) & 0xffu, x >> 24)));
+    }
+    return best;
+}
+
 // grid (tiles of both halves, image rows).  A workgroup owns up to 256 consecutive pixels of one half in one image row; tiles end on footprint
 // boundaries, so no footprint straddles two of them.  Pass 1: the element-wise max of the footprint's ring rows over the tile's texel span, in
 // 16-byte loads (rows have a 16-byte pitch), into LDS; the bytes outside the span are cleared.  One barrier.  Pass 2: each work-item scans its pixel's
@@ -283,10 +333,9 @@ __device__ __forceinline__ int4 wf_keep_bytes16(int4 v, int lo, int hi) {
 // span does not fit the slots (the host then makes the tile that one pixel) is folded: slot s holds the max of chunks s, s + slots, ...
 CSDR_KERNEL_WF __launch_bounds__(kWfThreads) void wf_view_peak(WfViewArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
+    const uint32_t *tab = wf_stage_table(smem, a.table);
     int4 *span = reinterpret_cast<int4 *>(smem + 256 * sizeof(uint32_t));
     const int tid = (int)threadIdx.x;
-    if (tid < 64) reinterpret_cast<int4 *>(tab)[tid] = reinterpret_cast<const int4 *>(a.table)[tid];
     const int h = (int)blockIdx.x >= a.tiles0 ? 1 : 0;
     const int per = h ? a.tile1 : a.tile0, nh = h ? a.width - a.n0 : a.n0;
     const int k0 = (h ? (int)blockIdx.x - a.tiles0 : (int)blockIdx.x) * per;
@@ -302,12 +351,7 @@ CSDR_KERNEL_WF __launch_bounds__(kWfThreads) void wf_view_peak(WfViewArgs a) {
     for (int s = tid; s < nslots; s += kWfThreads) {
         int4 acc = make_int4(0, 0, 0, 0);
         for (int cc = s; cc < nchunks; cc += a.slots) {               // (a second turn only when folded)
-            int rr = row0;
-            int4 m = *reinterpret_cast<const int4 *>(ring + (int64_t)rr * a.pitch + 16 * (int64_t)cc);
-            for (int r = 1; r < rt.count; ++r) {
-                if (++rr == a.lines) rr = 0;
-                m = wf_max_u8x16(m, *reinterpret_cast<const int4 *>(ring + (int64_t)rr * a.pitch + 16 * (int64_t)cc));
-            }
+            int4 m = wf_footprint_max(ring + 16 * (int64_t)cc, a.pitch, a.lines, row0, rt.count);
             if (cc == 0) m = wf_keep_bytes16(m, t0 - 16 * c0, 16);
             if (cc == nchunks - 1) m = wf_keep_bytes16(m, 0, t1 - 16 * (c0 + cc));
             acc = wf_max_u8x16(acc, m);
@@ -318,13 +362,7 @@ CSDR_KERNEL_WF __launch_bounds__(kWfThreads) void wf_view_peak(WfViewArgs a) {
     if (tid >= kn) return;
     const csdr_view_tap t = cols[tid];
     const int s = fold ? 0 : t.first - 16 * c0, e = fold ? 16 * nslots : s + t.count;   // this pixel's bytes in LDS
-    const unsigned *words = reinterpret_cast<const unsigned *>(span);
-    unsigned best = 0;
-    for (int w = s >> 2; 4 * w < e; ++w) {
-        const unsigned x = words[w] & wf_keep_bytes(s - 4 * w, e - 4 * w);
-        best = max(best, max(max(x & 0xffu, (x >> 8) & 0xffu), max((x >> 16) & 0xffu, x >> 24)));
-    }
-    a.out[(int64_t)blockIdx.y * a.width + (h ? a.n0 : 0) + k0 + tid] = tab[best];
+    a.out[(int64_t)blockIdx.y * a.width + (h ? a.n0 : 0) + k0 + tid] = tab[wf_scan_max(reinterpret_cast<const unsigned *>(span), s, e)];
 }
 
 }  // namespace csdr

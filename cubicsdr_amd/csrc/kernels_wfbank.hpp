@@ -5,8 +5,9 @@
 //   the slots' rings as one atlas of W x H      src/panel/WaterfallPanel.cpp:117-120,         wfb_view_linear (the reference's picture per tile)
 //     tiles                                     :161-219                                      wfb_view_peak   (the library's own: max over the footprint)
 //
-// The arithmetic is that of kernels_waterfall.hpp and is stated there once: wf_index, wf_blend, wf_max_u8x16, wf_keep_bytes are called from here.
-// What differs is where a work-item finds its slot: in a record the host uploads with the call (csdr_wfbank.hip does all integer bookkeeping), so
+// Every kernel body here is that of kernels_waterfall.hpp and is stated there once: wf_quantize_chunk, wf_stage_table, wf_linear4,
+// wf_store4, wf_footprint_max and wf_scan_max are called from here, as they are from the single panel's kernels.  What a kernel of this file keeps
+// is where a work-item finds its slot: in a record the host uploads with the call (csdr_wfbank.hip does all integer bookkeeping), so
 // the grid covers all slots at once.  Pending rows and ring rows keep the 16-byte pitch; a slot's pending block is max_pending * pitch bytes per
 // half and its ring block lines * pitch, both multiples of 16, so every row of every slot starts on a 16-byte boundary.
 // Home unit: csdr_wfbank.hip.
@@ -53,43 +54,9 @@ CSDR_KERNEL_WFB __launch_bounds__(kWfThreads) void wfb_quantize(WfbQuantArgs a) 
     const int p0 = j * a.half + i0;                                   // byte i of half j comes from point j * half + i (:65-67)
     for (int q = (int)blockIdx.y; q < a.n_jobs; q += (int)gridDim.y) {
         const WfbJob jb = a.jobs[q];
-        const bool pair = (jb.flags & kWfbPair) != 0, wide = (jb.flags & kWfbWide) != 0 && cnt == kWfChunk;
-        float v[kWfChunk];
-        if (wide) {
-            if (pair) {
-                const float4 *s = reinterpret_cast<const float4 *>(jb.src + 2 * (int64_t)p0);
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { float4 t = s[k]; pin_loaded(t); v[2 * k] = t.y; v[2 * k + 1] = t.w; }      // (pinned: whole 16-byte loads, as in wf_quantize)
-            } else {
-                const float4 *s = reinterpret_cast<const float4 *>(jb.src + p0);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { const float4 t = s[k]; v[4 * k] = t.x; v[4 * k + 1] = t.y; v[4 * k + 2] = t.z; v[4 * k + 3] = t.w; }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < kWfChunk; ++k) v[k] = k < cnt ? jb.src[pair ? 2 * (int64_t)(p0 + k) + 1 : (int64_t)(p0 + k)] : 0.0f;
-        }
-        if (jb.row >= 0) {
-            unsigned w[4];
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) w[q4] = wf_index(v[4 * q4]) | (wf_index(v[4 * q4 + 1]) << 8) | (wf_index(v[4 * q4 + 2]) << 16) | (wf_index(v[4 * q4 + 3]) << 24);
-            uint8_t *row = a.pend + ((int64_t)jb.slot * 2 + j) * a.pend_half + (int64_t)jb.row * a.pitch + i0;          // 16-byte aligned: every term is
-            if (cnt == kWfChunk) *reinterpret_cast<int4 *>(row) = make_int4((int)w[0], (int)w[1], (int)w[2], (int)w[3]);
-            else {
-#pragma unroll
-                for (int k = 0; k < kWfChunk; ++k) if (k < cnt) row[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-            }
-        }
-        if (jb.keep) {
-            float *kp = jb.keep + p0;
-            if (wide) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) reinterpret_cast<float4 *>(kp)[k] = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < kWfChunk; ++k) if (k < cnt) kp[k] = v[k];
-            }
-        }
+        const bool wide = (jb.flags & kWfbWide) != 0 && cnt == kWfChunk;
+        wf_quantize_chunk(jb.src, (jb.flags & kWfbPair) != 0, HideDcSpan(), p0, cnt, wide, wide,
+                          jb.row >= 0, a.pend + ((int64_t)jb.slot * 2 + j) * a.pend_half + (int64_t)jb.row * a.pitch + i0, jb.keep);       // (the row is 16-byte aligned: every term is)
     }
 }
 
@@ -148,8 +115,7 @@ struct WfbViewArgs {
 // row by row, so a workgroup takes 256 / groups image rows of a thumbnail and none of it idles (a 64-pixel row is 16 work-items).
 CSDR_KERNEL_WFB __launch_bounds__(kWfThreads) void wfb_view_linear(WfbViewArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
-    if (threadIdx.x < 64) reinterpret_cast<int4 *>(tab)[threadIdx.x] = reinterpret_cast<const int4 *>(a.table)[threadIdx.x];
+    const uint32_t *tab = wf_stage_table(smem, a.table);
     __syncthreads();
     const int tile = (int)(blockIdx.x / (unsigned)a.per_tile);
     const int item = (int)(blockIdx.x % (unsigned)a.per_tile) * kWfThreads + (int)threadIdx.x;
@@ -160,25 +126,14 @@ CSDR_KERNEL_WFB __launch_bounds__(kWfThreads) void wfb_view_linear(WfbViewArgs a
     uint32_t c[4] = {0u, 0u, 0u, 0u};
     if (tl.ofs >= 0) {
         const uint8_t *ring0 = a.ring + (int64_t)tl.slot * 2 * a.ring_half;
-        const csdr_view_tap rt = a.rows[py];
-        const int j0 = (int)(((int64_t)tl.ofs + rt.first + a.lines) % a.lines), j1 = j0 + 1 == a.lines ? 0 : j0 + 1;     // GL_REPEAT
+        csdr_view_tap ct[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const csdr_view_tap t = a.cols[min(px0 + k, a.width - 1)];
-            const uint8_t *tex = ring0 + (t.half ? a.ring_half : (int64_t)0) + t.first;
-            const uint8_t *r0 = tex + (int64_t)j0 * a.pitch, *r1 = tex + (int64_t)j1 * a.pitch;
-            c[k] = wf_blend(tab[r0[0]], tab[r0[1]], tab[r1[0]], tab[r1[1]], t.frac, rt.frac);
-        }
+        for (int k = 0; k < 4; ++k) ct[k] = a.cols[min(px0 + k, a.width - 1)];
+        wf_linear4(tab, ring0, ring0 + a.ring_half, a.pitch, a.lines, tl.ofs, ct, a.rows[py], c);
     }
     const int64_t pic_w = (int64_t)a.atlas_cols * a.width;
-    const int64_t base = ((int64_t)(tile / a.atlas_cols) * a.height + py) * pic_w + (int64_t)(tile % a.atlas_cols) * a.width + px0;
-    uint32_t *o = a.out + base;
     // the ATLAS address decides: a tile whose width is no multiple of 4 leaves the tile columns beside it off the 16-byte grid
-    if (cnt == 4 && (base & 3) == 0) *reinterpret_cast<int4 *>(o) = make_int4((int)c[0], (int)c[1], (int)c[2], (int)c[3]);
-    else {
-#pragma unroll 1
-        for (int k = 0; k < cnt; ++k) o[k] = k == 0 ? c[0] : (k == 1 ? c[1] : (k == 2 ? c[2] : c[3]));        // (a loop that stays a loop, as in wf_rgba)
-    }
+    wf_store4(a.out, ((int64_t)(tile / a.atlas_cols) * a.height + py) * pic_w + (int64_t)(tile % a.atlas_cols) * a.width + px0, cnt, c[0], c[1], c[2], c[3]);
 }
 
 // grid (tiles, groups of rows_per image rows, 2 halves).  A workgroup owns rows_per image rows of one half of one tile.  Pass 1: for each of its
@@ -189,10 +144,9 @@ CSDR_KERNEL_WFB __launch_bounds__(kWfThreads) void wfb_view_linear(WfbViewArgs a
 // zero and no pixel's bytes reach into it.
 CSDR_KERNEL_WFB __launch_bounds__(kWfThreads) void wfb_view_peak(WfbViewArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
+    const uint32_t *tab = wf_stage_table(smem, a.table);
     int4 *span = reinterpret_cast<int4 *>(smem + 256 * sizeof(uint32_t));      // [rows_per][chunks]
     const int tid = (int)threadIdx.x;
-    if (tid < 64) reinterpret_cast<int4 *>(tab)[tid] = reinterpret_cast<const int4 *>(a.table)[tid];
     const int tile = (int)blockIdx.x, h = (int)blockIdx.z;
     const int py0 = (int)blockIdx.y * a.rows_per, nr = min(a.rows_per, a.height - py0);
     const WfbTile tl = a.tiles[tile];
@@ -201,13 +155,7 @@ CSDR_KERNEL_WFB __launch_bounds__(kWfThreads) void wfb_view_peak(WfbViewArgs a) 
         for (int s = tid; s < nr * a.chunks; s += kWfThreads) {
             const int r = s / a.chunks, cc = s - r * a.chunks;
             const csdr_view_tap rt = a.rows[py0 + r];
-            int rr = (int)(((int64_t)tl.ofs + rt.first) % a.lines);    // scrolled row q is ring row (ofs + q) mod lines
-            int4 m = *reinterpret_cast<const int4 *>(ring + (int64_t)rr * a.pitch + 16 * (int64_t)cc);
-            for (int q = 1; q < rt.count; ++q) {
-                if (++rr == a.lines) rr = 0;
-                m = wf_max_u8x16(m, *reinterpret_cast<const int4 *>(ring + (int64_t)rr * a.pitch + 16 * (int64_t)cc));
-            }
-            span[s] = m;
+            span[s] = wf_footprint_max(ring + 16 * (int64_t)cc, a.pitch, a.lines, (int)(((int64_t)tl.ofs + rt.first) % a.lines), rt.count);
         }
     }
     __syncthreads();
@@ -219,14 +167,7 @@ CSDR_KERNEL_WFB __launch_bounds__(kWfThreads) void wfb_view_peak(WfbViewArgs a) 
         uint32_t px = 0u;
         if (tl.ofs >= 0) {
             const csdr_view_tap t = a.cols[x0 + k];
-            const int s = t.first, e = s + t.count;                   // this pixel's bytes of the row in LDS
-            const unsigned *words = reinterpret_cast<const unsigned *>(span + r * a.chunks);
-            unsigned best = 0;
-            for (int w = s >> 2; 4 * w < e; ++w) {
-                const unsigned x = words[w] & wf_keep_bytes(s - 4 * w, e - 4 * w);
-                best = max(best, max(max(x & 0xffu, (x >> 8) & 0xffu), max((x >> 16) & 0xffu, x >> 24)));
-            }
-            px = tab[best];
+            px = tab[wf_scan_max(reinterpret_cast<const unsigned *>(span + r * a.chunks), t.first, t.first + t.count)];      // this pixel's bytes of the row in LDS
         }
         out[(int64_t)r * pic_w + k] = px;
     }
