@@ -101,6 +101,9 @@ extern "C" void csdr_bank_destroy(csdr_bank *b) {
         if (b->ev_iq_read[k]) (void)hipEventDestroy(b->ev_iq_read[k]);
     }
     if (b->ev_iq_ready) (void)hipEventDestroy(b->ev_iq_ready);
+    if (b->audio_read_pending) (void)hipEventSynchronize(b->ev_audio_read);
+    if (b->ev_audio_read) (void)hipEventDestroy(b->ev_audio_read);
+    if (b->ev_audio_ready) (void)hipEventDestroy(b->ev_audio_ready);
     for (auto &s : b->slots) if (s.slab) (void)hipFree(s.slab);
     b->cfgs.release(); b->tables.release(); b->arms.release(); b->mconsts.release();
     for (int r = 0; r < kStageRing; ++r) {
@@ -679,6 +682,10 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
     if (int rc = c->signal(b->ev_fe_done[bpar], LANE_FE, LANE_AUDIO)) return rc;
     // lane AUDIO: modem + audio kernels of this batch
     if (int rc = c->wait(b->ev_fe_done[bpar], LANE_FE, LANE_AUDIO)) return rc;
+    if (b->audio_read_pending) {             // a device-side reader of the audio / scope taps (bank_audio_release): the kernels below rewrite them behind that reader
+        CSDR_HIP_TRY(hipStreamWaitEvent(st_a, b->ev_audio_read, 0));
+        b->audio_read_pending = false;
+    }
     if (fused1) {
         if (n_audio_run > 0)
             CSDR_LAUNCH(c, LANE_AUDIO, KID_AUDIO, demod_modem_audio1, dim3(n_audio_run), dim3(audio_threads), std::max(modem_lds, audio_lds), b->cfgs.p, dyns_d, lists_d, plans_d,
@@ -732,6 +739,23 @@ int bank_iq_release(csdr_bank *b, hipStream_t reader) {
     const int par = (int)((b->seq - 1) & 1); // the batch that was read; a slot's buffer of that batch is rewritten two of the slot's batches later at the earliest
     CSDR_HIP_TRY(hipEventRecord(b->ev_iq_read[par], reader));
     b->iq_read_pending[par] = true;
+    return CSDR_OK;
+}
+
+// ---- the audio and scope taps of the last execute for a reader that stays on the device (csdr_objects.hpp) ----
+int bank_audio_acquire(csdr_bank *b, hipStream_t reader) {
+    if (!b || b->last_nb == 0) return fail(CSDR_ESTATE, "no csdr_bank_execute yet");
+    if (!b->ev_audio_ready) {
+        CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_audio_ready, hipEventDisableTiming));
+        CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_audio_read, hipEventDisableTiming));
+    }
+    CSDR_HIP_TRY(hipEventRecord(b->ev_audio_ready, b->ctx->lanes[LANE_AUDIO]));
+    CSDR_HIP_TRY(hipStreamWaitEvent(reader, b->ev_audio_ready, 0));
+    return CSDR_OK;
+}
+int bank_audio_release(csdr_bank *b, hipStream_t reader) {
+    CSDR_HIP_TRY(hipEventRecord(b->ev_audio_read, reader));
+    b->audio_read_pending = true;
     return CSDR_OK;
 }
 

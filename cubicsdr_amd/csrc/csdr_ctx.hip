@@ -147,7 +147,8 @@ static const char *kKernelNames[KID_COUNT] = {
     "wf_quantize", "wf_update", "wf_rgba", "wf_view_linear", "wf_view_peak",
     "distrib_gather",
     "specbank_process",
-    "wfb_quantize", "wfb_update", "wfb_view_linear", "wfb_view_peak"};
+    "wfb_quantize", "wfb_update", "wfb_view_linear", "wfb_view_peak",
+    "scopebank_wave", "scopebank_spectrum"};
 static int prof_drain(csdr_ctx *c) {
     if (int rc = c->sync_all()) return rc;
     std::lock_guard<std::mutex> lk(c->prof_mu);

@@ -10,6 +10,7 @@
 #include <deque>
 #include <memory>
 
+#define CSDR_TU_IO 1     // this unit is the home of its kernels (kernels_io.hpp)
 #include "csdr_objects.hpp"
 #include "kernels_io.hpp"
 

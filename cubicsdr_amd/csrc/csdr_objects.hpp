@@ -137,6 +137,10 @@ struct csdr_bank {
     // batch it read.  Created at the first acquire: a bank nobody reads this way never has them
     hipEvent_t ev_iq_ready = nullptr, ev_iq_read[2] = {nullptr, nullptr};
     bool iq_read_pending[2] = {false, false};    // ev_iq_read[k] is recorded and not yet waited for
+    // the same for the slots' audio and scope taps (bank_audio_acquire / _release: the scope bank on its own stream).  SlotCfg::audio and ::scope are
+    // single-buffered: the NEXT execute's modem / audio lane waits for the reader
+    hipEvent_t ev_audio_ready = nullptr, ev_audio_read = nullptr;
+    bool audio_read_pending = false;             // ev_audio_read is recorded and not yet waited for
 };
 
 // =================================================================================================== spectrum points for device-side readers
@@ -172,6 +176,14 @@ int bank_iq_acquire(csdr_bank *b, hipStream_t reader);
 int bank_iq_release(csdr_bank *b, hipStream_t reader);
 // block bb of a slot's last execute inside that buffer: the samples in front of it are the earlier blocks' (BlockPlan::j0, batch-relative from 0)
 static inline const float2 *bank_slot_iq(const SlotHost &s) { return s.cfg.iq + (size_t)s.last_parity * ((size_t)kIqHist + s.cfg.cap_iq) + kIqHist; }
+
+// =================================================================================================== audio and scope taps for device-side readers
+// The audio side's counterpart: the slots' audio and scope taps of the last execute (where csdr_bank_scope_frame points), for a reader that stays in
+// HBM (csdr_scopebank_process_bank).  `reader` is made to wait for the modem / audio kernels of that execute by an event (no host synchronisation);
+// after enqueueing its reads the reader calls bank_audio_release, and the very next execute -- these buffers are single -- makes its modem / audio
+// lane wait for them before it rewrites the taps.  (csdr_bank.hip)
+int bank_audio_acquire(csdr_bank *b, hipStream_t reader);
+int bank_audio_release(csdr_bank *b, hipStream_t reader);
 
 // internal modem id: NCO + msresamp only, no modem / audio stage (the zoomed spectrum view's shift + resample, SpectrumVisualProcessor.cpp:306-379)
 #define CSDR_MODEM_FRONTEND_ONLY 100

@@ -14,6 +14,13 @@
 #include "kernels_post.hpp"
 #include "kernels_spec.hpp"
 
+// the kernels that are not templates have ONE home, csdr_io.hip (common.hpp); csdr_scopebank.hip includes this header for the frame bodies of the scope
+#if defined(CSDR_TU_IO)
+#define CSDR_KERNEL_IO CSDR_KERNEL
+#else
+#define CSDR_KERNEL_IO CSDR_KERNEL_ELSEWHERE
+#endif
+
 namespace csdr {
 
 // ---- one AudioThreadInput as the scope sees it ------------------------------------------------------------------------------
@@ -51,15 +58,12 @@ struct ScopeMeta {               // per produced item
 };
 
 constexpr int kScopeThreads = 256;
+struct ScopeTrk { double ceil_ma, ceil_maa, floor_ma, floor_maa; };        // the four trackers (:11-12, :186-190)
 
-// ---- waveform (:64-117).  grid = frames.  points[f] has room for 2 * max_n floats ------------------------------------------------
-CSDR_KERNEL __launch_bounds__(kScopeThreads) void scope_wave(const ScopeFrame *__restrict__ frames, int max_scope_samples, int max_n,
-                                                            float *__restrict__ points, ScopeMeta *__restrict__ meta) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float *s_red = reinterpret_cast<float *>(smem);
-    const ScopeFrame fr = scope_load(frames, blockIdx.x);
+// ---- the waveform item of ONE frame (:64-117), by one workgroup of kScopeThreads; `out` has room for 2 * max_n floats, s_red for four floats.
+// The statements of scope_wave and of scopebank_wave (kernels_scopebank.hpp): written once.
+__device__ __forceinline__ void scope_wave_frame(const ScopeFrame &fr, int max_scope_samples, float *__restrict__ out, ScopeMeta *__restrict__ meta, float *s_red) {
     const int tid = threadIdx.x;
-    float *out = points + (size_t)blockIdx.x * 2 * max_n;
     const int shown = min(fr.n, max_scope_samples);                       // iMax of the peak search and of the plain Y trace
     float pk = 1.0f;                                                       // "float peak = 1.0f": quiet frames are not blown up
     for (int i = tid; i < shown; i += kScopeThreads) pk = fmaxf(pk, fabsf(scope_at(fr, i)));
@@ -95,69 +99,86 @@ CSDR_KERNEL __launch_bounds__(kScopeThreads) void scope_wave(const ScopeFrame *_
         ScopeMeta m;
         m.mode = mode; m.spectrum = 0; m.channels = fr.channels; m.input_rate = fr.input_rate; m.sample_rate = fr.sample_rate;
         m.fft_size = 0; m.n_floats = n_floats; m.pad = 0; m.fft_floor = 0.0; m.fft_ceil = 0.0;
-        meta[blockIdx.x] = m;
+        *meta = m;
     }
+}
+
+// ---- waveform (:64-117).  grid = frames.  points[f] has room for 2 * max_n floats ------------------------------------------------
+CSDR_KERNEL_IO __launch_bounds__(kScopeThreads) void scope_wave(const ScopeFrame *__restrict__ frames, int max_scope_samples, int max_n,
+                                                               float *__restrict__ points, ScopeMeta *__restrict__ meta) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const ScopeFrame fr = scope_load(frames, blockIdx.x);
+    scope_wave_frame(fr, max_scope_samples, points + (size_t)blockIdx.x * 2 * max_n, meta + blockIdx.x, reinterpret_cast<float *>(smem));
+}
+
+// ---- the spectrum item of ONE frame (:119-214), by one workgroup of kFftThreads that carries the trackers `t` in every thread: the frame's L
+// zero-padded reals through the in-LDS transform of the main spectrum (sa, sb: L float2 each), bins [0, L/2) kept; ma / maa double[L/2] are the
+// two averagers; `out` has room for L floats, s_red for eight doubles.  Ends in a barrier: the LDS arrays are free for the next frame.
+// The statements of scope_spectrum and of scopebank_spectrum (kernels_scopebank.hpp): written once.
+__device__ __forceinline__ void scope_spectrum_frame(const ScopeFrame &fr, int L, double rate, const float2 *__restrict__ tw4096, double *__restrict__ ma,
+                                                     double *__restrict__ maa, ScopeTrk &t, float *__restrict__ out, ScopeMeta *__restrict__ meta,
+                                                     float2 *sa, float2 *sb, double *s_red /* [2][4 waves] */) {
+    const int tid = threadIdx.x, H = L >> 1;
+    const int cnt = fr.channels == 2 ? (fr.n >> 1) : fr.n;                // samples per channel handed to the transform
+    for (int i = tid; i < L; i += kFftThreads) {
+        float v = 0.f;
+        if (i < cnt) v = fr.channels == 2 ? scope_at(fr, i) + scope_at(fr, cnt + i) : scope_at(fr, i);   // stereo: left + right (:132-141)
+        sa[i] = make_float2(v, 0.f);
+    }
+    __syncthreads();
+    const float2 *X = lds_fft(sa, sb, L, tw4096);
+    // magnitude -> first averager -> second averager (which sees the NEW first one, :176-177); extrema in double (:179-184)
+    double mx = 0.0, mn = 1.0;
+    for (int i = tid; i < H; i += kFftThreads) {
+        const double a = (double)X[i].x, b = (double)X[i].y;
+        const double mag = sqrt(a * a + b * b);
+        double m1 = ma[i], m2 = maa[i];
+        m1 += (mag - m1) * rate;
+        m2 += (m1 - m2) * rate;
+        ma[i] = m1; maa[i] = m2;
+        mx = fmax(mx, m2); mn = fmin(mn, m2);
+    }
+    for (int o = 32; o > 0; o >>= 1) { mx = fmax(mx, __shfl_down(mx, o, 64)); mn = fmin(mn, __shfl_down(mn, o, 64)); }
+    if ((tid & 63) == 0) { s_red[tid >> 6] = mx; s_red[4 + (tid >> 6)] = mn; }
+    __syncthreads();
+    mx = fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
+    mn = fmin(fmin(s_red[4], s_red[5]), fmin(s_red[6], s_red[7]));
+    t.ceil_ma = t.ceil_ma + (mx - t.ceil_ma) * 0.05;                       // every thread carries the four trackers (:186-190)
+    t.ceil_maa = t.ceil_maa + (t.ceil_ma - t.ceil_maa) * 0.05;
+    t.floor_ma = t.floor_ma + (mn - t.floor_ma) * 0.05;
+    t.floor_maa = t.floor_maa + (t.floor_ma - t.floor_maa) * 0.05;
+    const double lo = t.floor_maa - 0.75;
+    const double den = log10((t.ceil_maa + 0.25) - lo);
+    const int osz = min(fr.out_size, H);
+    __syncthreads();                                                        // every thread's maa[] store is visible
+    for (int i = tid; i < osz; i += kFftThreads) {
+        out[2 * i] = (float)((double)i / (double)osz);
+        out[2 * i + 1] = (float)(log10(maa[i] + 0.25 - lo) / den);
+    }
+    if (tid == 0) {
+        ScopeMeta m;
+        m.mode = 0; m.spectrum = 1; m.channels = fr.channels; m.input_rate = fr.input_rate; m.sample_rate = fr.sample_rate;
+        m.fft_size = H; m.n_floats = 2 * osz; m.pad = 0; m.fft_floor = t.floor_maa; m.fft_ceil = t.ceil_maa;
+        *meta = m;
+    }
+    __syncthreads();                                                        // the LDS arrays are reused by the next frame
 }
 
 // ---- audio spectrum (:119-214).  ONE workgroup walks the frames in order: the averagers and trackers are recurrences over them.
 // L = fftSize <= 4096 complex points through the in-LDS transform of the main spectrum; bins [0, L/2) are kept.
 // state: ma / maa double[L/2], trk = {ceil_ma, ceil_maa, floor_ma, floor_maa}.  points[f] has room for L floats.
-CSDR_KERNEL __launch_bounds__(kFftThreads) void scope_spectrum(const ScopeFrame *__restrict__ frames, int nf, int L, double rate,
-                                                             const float2 *__restrict__ tw4096, double *__restrict__ ma, double *__restrict__ maa,
-                                                             double *__restrict__ trk, float *__restrict__ points, ScopeMeta *__restrict__ meta) {
+CSDR_KERNEL_IO __launch_bounds__(kFftThreads) void scope_spectrum(const ScopeFrame *__restrict__ frames, int nf, int L, double rate,
+                                                                const float2 *__restrict__ tw4096, double *__restrict__ ma, double *__restrict__ maa,
+                                                                double *__restrict__ trk, float *__restrict__ points, ScopeMeta *__restrict__ meta) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *sa = reinterpret_cast<float2 *>(smem), *sb = sa + L;
     double *s_red = reinterpret_cast<double *>(sb + L);                    // [2][4 waves]
-    const int tid = threadIdx.x, H = L >> 1;
-    double t_ceil_ma = trk[0], t_ceil_maa = trk[1], t_floor_ma = trk[2], t_floor_maa = trk[3];
+    ScopeTrk t{trk[0], trk[1], trk[2], trk[3]};
     for (int f = 0; f < nf; ++f) {
         const ScopeFrame fr = scope_load(frames, f);
-        const int cnt = fr.channels == 2 ? (fr.n >> 1) : fr.n;            // samples per channel handed to the transform
-        for (int i = tid; i < L; i += kFftThreads) {
-            float v = 0.f;
-            if (i < cnt) v = fr.channels == 2 ? scope_at(fr, i) + scope_at(fr, cnt + i) : scope_at(fr, i);   // stereo: left + right (:132-141)
-            sa[i] = make_float2(v, 0.f);
-        }
-        __syncthreads();
-        const float2 *X = lds_fft(sa, sb, L, tw4096);
-        // magnitude -> first averager -> second averager (which sees the NEW first one, :176-177); extrema in double (:179-184)
-        double mx = 0.0, mn = 1.0;
-        for (int i = tid; i < H; i += kFftThreads) {
-            const double a = (double)X[i].x, b = (double)X[i].y;
-            const double mag = sqrt(a * a + b * b);
-            double m1 = ma[i], m2 = maa[i];
-            m1 += (mag - m1) * rate;
-            m2 += (m1 - m2) * rate;
-            ma[i] = m1; maa[i] = m2;
-            mx = fmax(mx, m2); mn = fmin(mn, m2);
-        }
-        for (int o = 32; o > 0; o >>= 1) { mx = fmax(mx, __shfl_down(mx, o, 64)); mn = fmin(mn, __shfl_down(mn, o, 64)); }
-        if ((tid & 63) == 0) { s_red[tid >> 6] = mx; s_red[4 + (tid >> 6)] = mn; }
-        __syncthreads();
-        mx = fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
-        mn = fmin(fmin(s_red[4], s_red[5]), fmin(s_red[6], s_red[7]));
-        t_ceil_ma = t_ceil_ma + (mx - t_ceil_ma) * 0.05;                   // every thread carries the four trackers (:186-190)
-        t_ceil_maa = t_ceil_maa + (t_ceil_ma - t_ceil_maa) * 0.05;
-        t_floor_ma = t_floor_ma + (mn - t_floor_ma) * 0.05;
-        t_floor_maa = t_floor_maa + (t_floor_ma - t_floor_maa) * 0.05;
-        const double lo = t_floor_maa - 0.75;
-        const double den = log10((t_ceil_maa + 0.25) - lo);
-        const int osz = min(fr.out_size, H);
-        float *out = points + (size_t)f * L;
-        __syncthreads();                                                    // every thread's maa[] store is visible
-        for (int i = tid; i < osz; i += kFftThreads) {
-            out[2 * i] = (float)((double)i / (double)osz);
-            out[2 * i + 1] = (float)(log10(maa[i] + 0.25 - lo) / den);
-        }
-        if (tid == 0) {
-            ScopeMeta m;
-            m.mode = 0; m.spectrum = 1; m.channels = fr.channels; m.input_rate = fr.input_rate; m.sample_rate = fr.sample_rate;
-            m.fft_size = H; m.n_floats = 2 * osz; m.pad = 0; m.fft_floor = t_floor_maa; m.fft_ceil = t_ceil_maa;
-            meta[f] = m;
-        }
-        __syncthreads();                                                    // the LDS arrays are reused by the next frame
+        scope_spectrum_frame(fr, L, rate, tw4096, ma, maa, t, points + (size_t)f * L, meta + f, sa, sb, s_red);
     }
-    if (tid == 0) { trk[0] = t_ceil_ma; trk[1] = t_ceil_maa; trk[2] = t_floor_ma; trk[3] = t_floor_maa; }
+    if (threadIdx.x == 0) { trk[0] = t.ceil_ma; trk[1] = t.ceil_maa; trk[2] = t.floor_ma; trk[3] = t.floor_maa; }
 }
 
 // ---- audio mix-down (audioCallback) ---------------------------------------------------------------------------------------
@@ -184,7 +205,7 @@ struct MixBuffer { int32_t piece0, piece1, ref0, ref1, n_sources, pad; };
 constexpr int kMixThreads = 256;
 constexpr int kMixMaxSources = 1024;       // per buffer (LDS: one double each)
 
-CSDR_KERNEL __launch_bounds__(kMixThreads) void audio_mix(const MixBuffer *__restrict__ bufs, const MixPiece *__restrict__ pieces,
+CSDR_KERNEL_IO __launch_bounds__(kMixThreads) void audio_mix(const MixBuffer *__restrict__ bufs, const MixPiece *__restrict__ pieces,
                                                         const MixPeakRef *__restrict__ refs, int frames, float *__restrict__ out,
                                                         float *__restrict__ out_peak /* per buffer: the summed peak (diagnostic / PCM scale) */) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -225,7 +246,7 @@ CSDR_KERNEL __launch_bounds__(kMixThreads) void audio_mix(const MixBuffer *__res
 // append `n` floats at src to a ring at write position wpos (ring of mask + 1 floats); grid-stride.  One launch moves the batch audio
 // of many demodulators: job j = blockIdx.y.
 struct RingPush { const float *src; float *ring; uint32_t mask, wpos; int32_t n; int32_t n_peaks; const void *peaks_src /* BlockOut[n_peaks] */; float *peaks_dst; uint32_t peaks_mask, peaks_wpos; };
-CSDR_KERNEL __launch_bounds__(256) void ring_push(const RingPush *__restrict__ jobs, int peak_stride_bytes, int peak_offset_bytes) {
+CSDR_KERNEL_IO __launch_bounds__(256) void ring_push(const RingPush *__restrict__ jobs, int peak_stride_bytes, int peak_offset_bytes) {
     const RingPush jb = jobs[blockIdx.y];
     for (int i = blockIdx.x * 256 + threadIdx.x; i < jb.n; i += 256 * gridDim.x) jb.ring[(jb.wpos + (uint32_t)i) & jb.mask] = jb.src[i];
     if (blockIdx.x == 0)
@@ -236,7 +257,7 @@ CSDR_KERNEL __launch_bounds__(256) void ring_push(const RingPush *__restrict__ j
 
 // ---- float -> 16-bit PCM with the WAV writer's anti-clipping scale (:136): int(x * (peak < 1 ? 32767 : 32767 / peak)), low 16 bits.
 // job = one AudioThreadInput (a block): grid = (chunks, jobs)
-CSDR_KERNEL __launch_bounds__(256) void pcm16_convert(const PcmJob *__restrict__ jobs) {
+CSDR_KERNEL_IO __launch_bounds__(256) void pcm16_convert(const PcmJob *__restrict__ jobs) {
     const PcmJob jb = jobs[blockIdx.y];
     const float pk = *jb.peak;
     const float scale = pk < 1.0f ? 32767.0f : __fdiv_rn(32767.0f, pk);
@@ -246,7 +267,7 @@ CSDR_KERNEL __launch_bounds__(256) void pcm16_convert(const PcmJob *__restrict__
 
 // ---- ingest: host block -> HBM with I and Q exchanged on the way (the reference swaps while it copies the block together).
 // `src` is page-locked host memory mapped into the device's address space: the kernel IS the transfer over the link.
-CSDR_KERNEL __launch_bounds__(256) void ingest_swap(const float2 *src, float2 *dst /* may be src: exchange in place */, int64_t n) {
+CSDR_KERNEL_IO __launch_bounds__(256) void ingest_swap(const float2 *src, float2 *dst /* may be src: exchange in place */, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)256 * gridDim.x) {
         const float2 v = src[i];
         dst[i] = make_float2(v.y, v.x);

@@ -912,6 +912,86 @@ class ScopeProcessor:
             self.h = C.c_void_p()
 
 
+class ScopeBank:
+    """N independent ScopeVisualProcessors of one fft_size (csdr_scopebank): one per demodulator, all slots and all frames of a call in two launches;
+    state and items stay in HBM."""
+
+    def __init__(self, ctx, fft_size, max_slots, max_frames=1, max_samples=4096):
+        self._l = H.lib()
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        H.check(self._l.csdr_scopebank_create(ctx.h, C.byref(self.h)))
+        self.setup(fft_size, max_slots, max_frames, max_samples)
+
+    def setup(self, fft_size, max_slots, max_frames=1, max_samples=4096):
+        H.check(self._l.csdr_scopebank_setup(self.h, int(fft_size), int(max_slots), int(max_frames), int(max_samples)))
+        self.fft_size, self.max_slots, self.max_frames, self.max_samples = int(fft_size), int(max_slots), int(max_frames), int(max_samples)
+
+    def set_enabled(self, scope=True, spectrum=True):
+        H.check(self._l.csdr_scopebank_set_enabled(self.h, int(scope), int(spectrum)))
+
+    def set_max_scope_samples(self, n):
+        H.check(self._l.csdr_scopebank_set_max_scope_samples(self.h, int(n)))
+
+    def set_average_rate(self, r):
+        H.check(self._l.csdr_scopebank_set_average_rate(self.h, float(r)))
+
+    def reset_slot(self, slot):
+        H.check(self._l.csdr_scopebank_reset_slot(self.h, int(slot)))
+
+    def try_process(self, items):
+        """items: [(slot, frame)] with frame a dict as ScopeProcessor.process takes (host data), an H.ScopeFrame whose data lies in HBM
+        (DemodBank.scope_frame), or None for no input; host and device frames do not mix in one call -> the return code"""
+        arr = (H.ScopeBankItem * max(len(items), 1))()
+        keep = []
+        dev = any(isinstance(f, H.ScopeFrame) for _, f in items)
+        for k, (slot, f) in enumerate(items):
+            arr[k].slot = int(slot)
+            if f is None:
+                continue
+            if isinstance(f, H.ScopeFrame):
+                arr[k].frame = f
+                continue
+            if dev:
+                raise ValueError("host and device frames in one call")
+            a = np.ascontiguousarray(f["data"], dtype=np.float32)
+            keep.append(a)
+            arr[k].frame = H.ScopeFrame(a.ctypes.data if a.size else None, None, a.size, int(f["channels"]), int(f.get("type", 0)), int(f["sample_rate"]),
+                                        int(f["input_rate"]), int(f.get("layout", 0)), float(f.get("scale", 1.0)))
+        return self._l.csdr_scopebank_process(self.h, arr, len(items), 1 if dev else 0)
+
+    def process(self, items):
+        H.check(self.try_process(items))
+
+    def process_bank(self, bank):
+        """the scope tap of the bank's last execute, for every active slot the object has room for: one call, no host synchronisation"""
+        H.check(self._l.csdr_scopebank_process_bank(self.h, bank.h))
+
+    def frames(self, slot):
+        return self._l.csdr_scopebank_frames(self.h, int(slot))
+
+    def fetch(self, slot, frame, spectrum):
+        """-> the dict ScopeProcessor.fetch returns, or None when that half was switched off"""
+        pts = np.empty(max(2 * self.max_samples, self.fft_size), np.float32)
+        info = H.ScopeInfo()
+        H.check(self._l.csdr_scopebank_fetch(self.h, int(slot), int(frame), 1 if spectrum else 0, pts.ctypes.data_as(C.c_void_p), pts.size, C.byref(info)))
+        if info.n_floats == 0:
+            return None
+        return dict(points=pts[:info.n_floats].copy(), mode=info.mode, spectrum=bool(info.spectrum), channels=info.channels, input_rate=info.input_rate,
+                    sample_rate=info.sample_rate, fft_size=info.fft_size, fft_floor=info.fft_floor, fft_ceil=info.fft_ceil)
+
+    def device_points(self, slot, spectrum):
+        """(device pointer, frames, stride in floats) of the slot's items of the last call; the context's boundary stream waits for them"""
+        p, n, st = C.c_void_p(), C.c_int(), C.c_int()
+        H.check(self._l.csdr_scopebank_device_points(self.h, int(slot), 1 if spectrum else 0, C.byref(p), C.byref(n), C.byref(st)))
+        return p.value, n.value, st.value
+
+    def close(self):
+        if self.h:
+            self._l.csdr_scopebank_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class AudioMixer:
     """AudioThread's mixing callback (csdr_mix): per-source block queues, rings in HBM, bit-exact mix-down."""
 

@@ -103,6 +103,10 @@ class ScopeInfo(C.Structure):
                 ("fft_size", C.c_int32), ("n_floats", C.c_int32), ("reserved", C.c_int32), ("fft_floor", C.c_double), ("fft_ceil", C.c_double)]
 
 
+class ScopeBankItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("reserved", C.c_int32), ("frame", ScopeFrame)]
+
+
 _p, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 _pp = C.POINTER(C.c_void_p)
 
@@ -284,6 +288,18 @@ ABI = {
     "csdr_specbank_fetch": (_i, [_p, _i, _i, _p, _i, C.POINTER(_d), C.POINTER(_d)]),
     "csdr_specbank_fetch_hold": (_i, [_p, _i, _i, _p, _i, C.POINTER(_i)]),
     "csdr_specbank_device_points": (_i, [_p, _i, _pp, C.POINTER(_i)]),
+    "csdr_scopebank_create": (_i, [_p, _pp]),
+    "csdr_scopebank_destroy": (None, [_p]),
+    "csdr_scopebank_setup": (_i, [_p, _i, _i, _i, _i]),
+    "csdr_scopebank_set_enabled": (_i, [_p, _i, _i]),
+    "csdr_scopebank_set_max_scope_samples": (_i, [_p, _i]),
+    "csdr_scopebank_set_average_rate": (_i, [_p, _f]),
+    "csdr_scopebank_reset_slot": (_i, [_p, _i]),
+    "csdr_scopebank_process": (_i, [_p, C.POINTER(ScopeBankItem), _i, _i]),
+    "csdr_scopebank_process_bank": (_i, [_p, _p]),
+    "csdr_scopebank_frames": (_i, [_p, _i]),
+    "csdr_scopebank_fetch": (_i, [_p, _i, _i, _i, _p, _i, C.POINTER(ScopeInfo)]),
+    "csdr_scopebank_device_points": (_i, [_p, _i, _i, _pp, C.POINTER(_i), C.POINTER(_i)]),
     "csdr_wfbank_create": (_i, [_p, _pp]),
     "csdr_wfbank_destroy": (None, [_p]),
     "csdr_wfbank_setup": (_i, [_p, _i, _i, _i, _i]),

@@ -48,6 +48,7 @@ typedef struct csdr_waterfall csdr_waterfall; /* WaterfallPanel's arithmetic: qu
 typedef struct csdr_distrib csdr_distrib; /* FFTDataDistributor's line cutting: the waterfall feed, cut where the block lies in HBM */
 typedef struct csdr_specbank csdr_specbank; /* N x SpectrumVisualProcessor, one per demodulator: every slot and block of an execute in one launch */
 typedef struct csdr_wfbank csdr_wfbank;     /* N x WaterfallPanel, one per demodulator: every slot of a step, an update or a render in one launch */
+typedef struct csdr_scopebank csdr_scopebank; /* N x ScopeVisualProcessor, one per demodulator: every slot and frame of a call in two launches */
 
 /* ------------------------------------------------------------------ context */
 int         csdr_abi_version(void);
@@ -776,6 +777,72 @@ int  csdr_wfbank_offset(const csdr_wfbank *wb, int slot, int half);             
 int  csdr_wfbank_fetch_index(csdr_wfbank *wb, int slot, int half, uint8_t *out_u8, int64_t cap);
 int  csdr_wfbank_render(csdr_wfbank *wb, const int *slots, int n_slots, int width, int height, int mode, int atlas_cols, uint8_t *out_u8, int64_t cap);
 int  csdr_wfbank_device_view(csdr_wfbank *wb, const uint8_t **dev, int *pic_width, int *pic_height);
+
+/* ------------------------------------------------------------------ Scope bank: one ScopeVisualProcessor per demodulator
+ * The reference feeds the audio scope of the ACTIVE demodulator from the demodulator's audio tap (DemodulatorThread.cpp:240-316): one
+ * ScopeVisualProcessor (src/process/ScopeVisualProcessor.cpp:24-217; "ScopeVisualProcessor" above is the single object).  A csdr_scopebank holds
+ * max_slots of them, all of one fft_size L; the state of every slot and the items of every frame stay in HBM, and one call runs all slots and all
+ * frames it is given in TWO kernel launches (waveform, spectrum), whatever the slot count.  Every slot behaves exactly as one csdr_scope after
+ * csdr_scope_setup(L, ...) that receives the slot's frames in the order given, whatever lies between them: its items are that object's byte for byte.
+ * Lines are those of src/process/ScopeVisualProcessor.cpp.
+ * 1. Limits (setup :24-35 on every slot).  L takes the values csdr_scope_setup takes: a power of two, 4 <= L <= 4096, otherwise CSDR_EUNSUPPORTED;
+ *    1 <= max_slots <= 4096; max_frames >= 1 frames per slot and call; max_samples >= 1 floats per frame; otherwise CSDR_EINVAL.  Setup resets every
+ *    slot; the object's settings (item 4) survive it.
+ * 2. Frames.  An item is one AudioThreadInput for one slot, described by a csdr_scope_frame exactly as csdr_scope_process defines it: both layouts
+ *    of a stereo tap read in place, n_dev (device frames only), scale, the three `type`s, one or two channels.  data_is_dev says where the data of
+ *    ALL frames of the call lies.  THE LIBRARY'S OWN DEFINITION: an item with frame.n == 0 or frame.data == NULL is no input at all -- it touches no
+ *    state and produces no item (the reference discards such inputs before process() does anything, :53-61).
+ * 3. Per frame, literally what csdr_scope does (one statement of it serves both objects): the waveform item (:64-117) -- the peak search over
+ *    min(n, maxScopeSamples) samples starting from 1.0f, every sample divided by it, x positions of the modes Y / 2Y / XY -- and the spectrum item
+ *    (:119-214) -- the L zero-padded reals (stereo: left + right), fft_execute, the double magnitude, the two double averagers (the second sees the
+ *    UPDATED first, :176-177), double extrema, the four trackers at 0.05 from zero (:11-12, :186-190), log10 in double, and
+ *    outSize = floor(L/2 * sampleRate / inputRate) points in float arithmetic (:194-200).
+ * 4. Settings are per object, apply to every slot and are read by the next process call: csdr_scopebank_set_enabled (setScopeEnabled /
+ *    setSpectrumEnabled :37-43; a half that is off produces no item, and a spectrum that is off advances no averager), csdr_scopebank_set_max_scope_samples
+ *    (default DEFAULT_DMOD_FFT_SIZE = 1024, :13), csdr_scopebank_set_average_rate (default 0.65f, :10).
+ * 5. Slot life cycle.  csdr_scopebank_reset_slot makes a slot a fresh processor: both averagers and the four trackers zero; its neighbours are
+ *    untouched.  Slots are independent: what one slot is fed, and whether others are fed at all, changes no bit of another slot's items.
+ * 6. Refusals are whole-call -- they enqueue nothing and change nothing, in no slot: a slot out of range, channels not 1 or 2, a layout not 0 .. 2,
+ *    n < 0: CSDR_EINVAL; a frame of more than max_samples floats: CSDR_ERANGE; more than max_frames frames for one slot: CSDR_ERANGE.
+ * 7. process_bank.  After a csdr_bank_execute (CSDR_ESTATE before the first): every configured, active slot s below the smaller of the two objects'
+ *    slot counts gets one item -- the frame csdr_bank_scope_frame(bank, s) describes, read where it lies in HBM.  A slot whose frame has n = 0 gets
+ *    none: skipped blocks, front-end-only, host and digital slots.  A tap longer than max_samples refuses the call (item 6; the stereo tap is up to
+ *    4096 floats).  Both handles are used by this call.
+ * 8. Output.  csdr_scopebank_frames(slot) = the frames of the last process call for the slot; csdr_scopebank_fetch is csdr_scope_fetch per slot
+ *    (which = 0 the waveform, 1 the spectrum; info->n_floats == 0 when that half was switched off).  csdr_scopebank_device_points hands out the
+ *    slot's items of the last call where they lie in HBM: frame f at dev + f * stride_floats, stride_floats = L for the spectrum and
+ *    2 * max_samples for the waveform; *frames = 0 when that half was switched off.  The boundary stream is made to wait for them.  A spectrum frame
+ *    with sample_rate == input_rate holds L floats = L/2 (x, y) pairs: the pair layout csdr_wfbank_step / csdr_waterfall_step take for
+ *    fft_size = L/2 (n_floats_per_line = L), so an audio waterfall per demodulator needs no raster code of its own.
+ * 9. Not in this object: a raster of the waveform trace; the tap of blocks other than the last one of an execute (the reference's one-deep queue
+ *    shows at most one per display refresh); L above 4096.
+ * Ordering.  All work runs on a stream of the object's own, as the spectrum bank's does; the fetches synchronise it.  Host frames are copied into
+ * page-locked staging inside the call, so the caller's buffers are free when it returns; device frames must have been produced on the boundary stream
+ * and are ordered behind it by an event.  csdr_scopebank_process_bank orders itself behind the bank's modem / audio kernels by an event and leaves one
+ * that the bank's NEXT execute waits for on the device before it rewrites the taps (they are single-buffered): the two objects never synchronise the
+ * host for each other.  A call waits on the host only for the upload of its plan that last used the same page-locked staging set, two calls ago.
+ * The items are rewritten by the next process call.  A reader of the pointer csdr_scopebank_device_points hands out is NOT waited for: it has FINISHED
+ * before the next process, process_bank, setup or reset_slot of this object (csdr_waterfall_fetch_* or any other synchronising call on the reader's
+ * stream). */
+typedef struct csdr_scopebank_item {
+    int32_t slot;              /* 0 .. max_slots - 1 */
+    int32_t reserved;
+    csdr_scope_frame frame;    /* one AudioThreadInput; n == 0 or data == NULL: no input */
+} csdr_scopebank_item;
+CSDR_STATIC_ASSERT(sizeof(csdr_scopebank_item) == 56 && offsetof(csdr_scopebank_item, frame) == 8, "csdr_scopebank_item layout");
+int  csdr_scopebank_create(csdr_ctx *ctx, csdr_scopebank **out);
+void csdr_scopebank_destroy(csdr_scopebank *sb);
+int  csdr_scopebank_setup(csdr_scopebank *sb, int fft_size, int max_slots, int max_frames, int max_samples);
+int  csdr_scopebank_set_enabled(csdr_scopebank *sb, int scope_enabled, int spectrum_enabled);  /* :37-43, on every slot */
+int  csdr_scopebank_set_max_scope_samples(csdr_scopebank *sb, int n);                          /* maxScopeSamples, default 1024 (:13) */
+int  csdr_scopebank_set_average_rate(csdr_scopebank *sb, float rate);                          /* fft_average_rate, default 0.65 (:10) */
+int  csdr_scopebank_reset_slot(csdr_scopebank *sb, int slot);
+/* n_items AudioThreadInputs; the items of one slot are its frames in the order given */
+int  csdr_scopebank_process(csdr_scopebank *sb, const csdr_scopebank_item *items, int n_items, int data_is_dev);
+int  csdr_scopebank_process_bank(csdr_scopebank *sb, csdr_bank *bank);                         /* both handles are used by this call */
+int  csdr_scopebank_frames(const csdr_scopebank *sb, int slot);                                /* frames of the last process call for the slot */
+int  csdr_scopebank_fetch(csdr_scopebank *sb, int slot, int frame, int which, float *points_host, int cap_floats, csdr_scope_info *info);
+int  csdr_scopebank_device_points(csdr_scopebank *sb, int slot, int which, const float **dev, int *frames, int *stride_floats);
 
 /* ------------------------------------------------------------------ audio egress
  * csdr_mix replaces the arithmetic AND the queue rules of audioCallback (src/audio/AudioThread.cpp:88-240): sources in binding order;
