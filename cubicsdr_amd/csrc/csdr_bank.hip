@@ -104,6 +104,10 @@ extern "C" void csdr_bank_destroy(csdr_bank *b) {
     if (b->audio_read_pending) (void)hipEventSynchronize(b->ev_audio_read);
     if (b->ev_audio_read) (void)hipEventDestroy(b->ev_audio_read);
     if (b->ev_audio_ready) (void)hipEventDestroy(b->ev_audio_ready);
+    for (int k = 0; k < 2; ++k) {
+        if (b->plan_read_pending[k]) (void)hipEventSynchronize(b->ev_plan_read[k]);
+        if (b->ev_plan_read[k]) (void)hipEventDestroy(b->ev_plan_read[k]);
+    }
     for (auto &s : b->slots) if (s.slab) (void)hipFree(s.slab);
     b->cfgs.release(); b->tables.release(); b->arms.release(); b->mconsts.release();
     for (int r = 0; r < kStageRing; ++r) {
@@ -340,6 +344,7 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
         return rc;
     };
     b->dig_run.clear();
+    b->n_exec++;                             // from here on "the last execute" is this one: what a squelch bank took from the previous one is stale
     for (int si = 0; si < b->max_demods; ++si) {
         SlotHost &s = b->slots[si];
         s.results.clear(); s.last_J = 0; s.last_A = 0;
@@ -392,6 +397,7 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
         // floats written per arbitrary-stage output = 2^ash: an interpolating audio resampler fans every arbitrary-stage output out to
         // 2^aS samples; I/Q and FM stereo write two floats per sample (FM stereo with either kind of resampler, ModemFMStereo.cpp:91-105)
         const int ash = iq_modem ? 1 : (au_interp ? aS : 0) + (fms ? 1 : 0);
+        s.last_ash = fe_only ? -1 : ash;
         const bool iq_interp = s.iq.interp;      // arbitrary stage first: it consumes the channel samples directly, each output fans out to 2^S
         for (int bb = 0; bb <= NB; ++bb) {
             const int64_t K = iq_interp ? (int64_t)bb * Bc : (((int64_t)s.buf_idx + (int64_t)bb * Bc) >> S);
@@ -544,6 +550,10 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
         // (the device copy of this parity was last read by the audio kernels two batches ago: the demodulators' stream orders that by itself,
         //  the channelizer's stream waits for the event recorded behind them)
         if (fetch_on_post && b->tables_read_pending[bpar]) CSDR_HIP_TRY(hipStreamWaitEvent(c->lanes[LANE_POST], b->ev_tables_read[bpar], 0));
+        if (b->plan_read_pending[bpar]) {    // a device-side reader of this copy's block plan (bank_plan_release): the fetch rewrites it behind that reader
+            CSDR_HIP_TRY(hipStreamWaitEvent(fetch_on_post ? c->lanes[LANE_POST] : st, b->ev_plan_read[bpar], 0));
+            b->plan_read_pending[bpar] = false;
+        }
         CSDR_LAUNCH(c, fetch_on_post ? LANE_POST : LANE_FE, KID_TABLES, bank_tables_fetch, dim3(std::max(1, std::min(64, (n16 + 255) / 256))), dim3(256), 0,
                     reinterpret_cast<const float4 *>(table_h), reinterpret_cast<float4 *>(table_d), n16);
         CSDR_HIP_TRY(hipGetLastError());
@@ -754,8 +764,20 @@ int bank_audio_acquire(csdr_bank *b, hipStream_t reader) {
     return CSDR_OK;
 }
 int bank_audio_release(csdr_bank *b, hipStream_t reader) {
+    // ONE event stands for every reader of a batch: a second reader (a scope bank and a squelch bank behind the same execute) first waits for the
+    // first one's mark, so that the mark it leaves covers both
+    if (b->audio_read_pending) CSDR_HIP_TRY(hipStreamWaitEvent(reader, b->ev_audio_read, 0));
     CSDR_HIP_TRY(hipEventRecord(b->ev_audio_read, reader));
     b->audio_read_pending = true;
+    return CSDR_OK;
+}
+int bank_plan_release(csdr_bank *b, hipStream_t reader) {
+    if (b->seq == 0) return CSDR_OK;         // no batch has run a slot: nothing was read
+    const int par = (int)((b->seq - 1) & 1);
+    if (!b->ev_plan_read[par]) CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_plan_read[par], hipEventDisableTiming));
+    if (b->plan_read_pending[par]) CSDR_HIP_TRY(hipStreamWaitEvent(reader, b->ev_plan_read[par], 0));
+    CSDR_HIP_TRY(hipEventRecord(b->ev_plan_read[par], reader));
+    b->plan_read_pending[par] = true;
     return CSDR_OK;
 }
 

@@ -148,7 +148,8 @@ static const char *kKernelNames[KID_COUNT] = {
     "distrib_gather",
     "specbank_process",
     "wfb_quantize", "wfb_update", "wfb_view_linear", "wfb_view_peak",
-    "scopebank_wave", "scopebank_spectrum"};
+    "scopebank_wave", "scopebank_spectrum",
+    "squelch_scan", "squelch_pack", "squelch_pcm16"};
 static int prof_drain(csdr_ctx *c) {
     if (int rc = c->sync_all()) return rc;
     std::lock_guard<std::mutex> lk(c->prof_mu);

@@ -344,6 +344,63 @@ extern "C" int csdr_mix_push_bank(csdr_mix *m, csdr_bank *b, const int *slots, c
     CSDR_HIP_TRY(hipGetLastError());
     return CSDR_OK;
 }
+// csdr_mix_push_bank for the blocks the squelch bank left open (flag bit 2: !squelched && !muted, DemodulatorThread.cpp:318-328): one queue entry per
+// open block, in order, with its own peak -- the entries csdr_mix_push would have made block by block; one ring_push job per run of consecutive open
+// blocks.  The queue bookkeeping is host state: the flags come from the squelch bank's one copy per process (squelch_bank_flags).
+extern "C" int csdr_mix_push_squelched(csdr_mix *m, csdr_bank *b, csdr_squelch *sq, const int *slots, const int *sources, int n) {
+    DeviceScope dev__(m ? m->ctx : nullptr);
+    if (!m || !b || !sq || !slots || !sources || n <= 0) return fail(CSDR_EINVAL, "bad argument");
+    if (b->ctx != m->ctx) return fail(CSDR_EINVAL, "bank and mixer belong to different contexts");
+    for (int i = 0; i < n; ++i) {                    // every pair is checked before anything is enqueued
+        if (slots[i] < 0 || slots[i] >= b->max_demods || sources[i] < 0 || sources[i] >= (int)m->src.size()) return fail(CSDR_EINVAL, "pair %d", i);
+        if (!m->src[(size_t)sources[i]].bound) return fail(CSDR_ESTATE, "source %d is not bound", sources[i]);
+    }
+    const uint8_t *flags = nullptr;
+    int sq_slots = 0, stride = 0;
+    if (int rc = squelch_bank_flags(sq, b, &flags, &sq_slots, &stride)) return rc;
+    std::vector<RingPush> jobs;
+    int max_n = 0;
+    struct Undo { MixSource *s; uint32_t wpos, pwpos; size_t qsize; int64_t buffered; };
+    std::vector<Undo> undo;
+    for (int i = 0; i < n; ++i) {
+        const SlotHost &sl = b->slots[(size_t)slots[i]];
+        MixSource &s = m->src[(size_t)sources[i]];
+        if (!sl.configured || sl.results.empty() || sl.results[0].skipped || is_fe_only(sl.prm.modem)) continue;
+        if (slots[i] >= sq_slots || csdr_squelch_blocks(sq, slots[i]) != (int)sl.results.size()) continue;      // not stepped: nothing is open
+        const uint8_t *fl = flags + (size_t)slots[i] * (size_t)stride;
+        const int channels = (sl.prm.modem == CSDR_MODEM_IQ || sl.prm.modem == CSDR_MODEM_FMS) ? 2 : 1;
+        undo.push_back(Undo{&s, s.wpos, s.pwpos, s.queue.size(), s.buffered});
+        RingPush jb{};
+        auto flush = [&]() { if (jb.n_peaks) { jobs.push_back(jb); max_n = std::max(max_n, jb.n); } jb.n_peaks = 0; };
+        for (size_t k = 0; k < sl.results.size(); ++k) {
+            const csdr_block_result &r = sl.results[k];
+            if (!(fl[k] & CSDR_SQUELCH_OPEN)) { flush(); continue; }
+            if (!jb.n_peaks) {                        // a run of open blocks starts here
+                jb.src = sl.cfg.audio + r.audio_offset; jb.ring = s.ring.p; jb.mask = s.mask; jb.wpos = s.wpos; jb.n = 0;
+                jb.peaks_src = sl.cfg.bout + k; jb.peaks_dst = s.peaks.p; jb.peaks_mask = s.pmask; jb.peaks_wpos = s.pwpos;
+            }
+            const int rc = mix_enqueue(m, s, r.n_audio, channels, sl.prm.audio_sample_rate);
+            if (rc < 0) {                             // ring overrun: the copy kernel will not run, so nothing of this call may stay queued
+                for (const Undo &u : undo) { u.s->queue.resize(u.qsize); u.s->wpos = u.wpos; u.s->pwpos = u.pwpos; u.s->buffered = u.buffered; }
+                return rc;
+            }
+            if (rc == 1) break;                       // a full queue: stop at the first refusal, as csdr_mix_push_bank does
+            jb.n += r.n_audio; jb.n_peaks += 1;
+        }
+        flush();
+    }
+    if (jobs.empty()) return CSDR_OK;
+    csdr_ctx *c = m->ctx;
+    hipStream_t st = c->lanes[LANE_AUDIO];
+    if (int rc = m->push_d.reserve(std::max<size_t>(jobs.size(), 256))) return rc;
+    CSDR_HIP_TRY(hipMemcpyAsync(m->push_d.p, jobs.data(), jobs.size() * sizeof(RingPush), hipMemcpyHostToDevice, st));
+    CSDR_HIP_TRY(hipStreamSynchronize(st));                                       // (`jobs` is pageable and local)
+    for (size_t j0 = 0; j0 < jobs.size(); j0 += 65535)                             // (a grid's y extent; 1024 slots of 128 alternating blocks pass it)
+        CSDR_LAUNCH(c, LANE_AUDIO, KID_MIX, ring_push, dim3((unsigned)std::max(1, std::min(64, (max_n + 255) / 256)), (unsigned)std::min<size_t>(65535, jobs.size() - j0)), dim3(256), 0,
+                    m->push_d.p + j0, (int)sizeof(BlockOut), (int)offsetof(BlockOut, audio_peak));
+    CSDR_HIP_TRY(hipGetLastError());
+    return CSDR_OK;
+}
 extern "C" int csdr_mix_queued(const csdr_mix *m, int source) {
     if (!m || source < 0 || source >= (int)m->src.size()) return 0;
     return (int)m->src[(size_t)source].queue.size();

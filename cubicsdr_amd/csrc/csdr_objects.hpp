@@ -83,7 +83,8 @@ struct SlotHost {
     // results of the last execute
     std::vector<csdr_block_result> results;
     int last_J = 0, last_A = 0;
-    std::shared_ptr<DigSlot> dig;            // CSDR_MODEM_DIGITAL: the decision stage behind the front-end
+    int last_ash = -1;                       // floats per audio-arbitrary output of the last execute = 2^last_ash; -1: no audio stage ran
+    std::shared_ptr<DigSlot> dig;           // CSDR_MODEM_DIGITAL: the decision stage behind the front-end
 };
 constexpr int kStageRing = 4;                // pinned staging sets for the per-batch uploads
 }  // namespace csdr
@@ -141,6 +142,11 @@ struct csdr_bank {
     // single-buffered: the NEXT execute's modem / audio lane waits for the reader
     hipEvent_t ev_audio_ready = nullptr, ev_audio_read = nullptr;
     bool audio_read_pending = false;             // ev_audio_read is recorded and not yet waited for
+    // the same for a batch's block plan in the device tables (bank_plan_release: the squelch bank), by parity of the batch that was read: the
+    // execute that refetches that copy of the tables -- the second one after -- waits for the reader
+    hipEvent_t ev_plan_read[2] = {nullptr, nullptr};
+    bool plan_read_pending[2] = {false, false};
+    uint64_t n_exec = 0;                         // csdr_bank_execute calls that got as far as clearing the slots' results: what a reader of "the last execute" was taken from
 };
 
 // =================================================================================================== spectrum points for device-side readers
@@ -184,6 +190,16 @@ static inline const float2 *bank_slot_iq(const SlotHost &s) { return s.cfg.iq + 
 // lane wait for them before it rewrites the taps.  (csdr_bank.hip)
 int bank_audio_acquire(csdr_bank *b, hipStream_t reader);
 int bank_audio_release(csdr_bank *b, hipStream_t reader);
+// The block plan of the last execute that ran a slot, where it lies in the device tables: slot s at bank_last_plans(b) + s * (last_nb + 1).  It was
+// fetched on the front-end's lane in front of the kernels bank_audio_acquire orders the reader behind; after enqueueing its reads the reader calls
+// bank_plan_release, and the execute that refetches that copy of the tables waits for them.  (csdr_bank.hip)
+static inline const BlockPlan *bank_last_plans(const csdr_bank *b) { return b->plans_of(b->tables.p + (size_t)((b->seq - 1) & 1) * b->table_bytes); }
+int bank_plan_release(csdr_bank *b, hipStream_t reader);
+
+// =================================================================================================== squelch flags for the mixer
+// The flags of the squelch bank's last process, [max_slots][stride] on the host (csdr_squelch_fetch_flags' copy, cached until the next process), for
+// csdr_mix_push_squelched: CSDR_ESTATE unless that process was csdr_squelch_process_bank of `bank`'s last execute.  (csdr_squelch.hip)
+int squelch_bank_flags(csdr_squelch *sq, const csdr_bank *bank, const uint8_t **flags, int *max_slots, int *stride);
 
 // internal modem id: NCO + msresamp only, no modem / audio stage (the zoomed spectrum view's shift + resample, SpectrumVisualProcessor.cpp:306-379)
 #define CSDR_MODEM_FRONTEND_ONLY 100

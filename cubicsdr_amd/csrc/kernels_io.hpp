@@ -256,13 +256,15 @@ CSDR_KERNEL_IO __launch_bounds__(256) void ring_push(const RingPush *__restrict_
 }
 
 // ---- float -> 16-bit PCM with the WAV writer's anti-clipping scale (:136): int(x * (peak < 1 ? 32767 : 32767 / peak)), low 16 bits.
+// The two statements, which pcm16_convert and the squelch bank's recorder (kernels_squelch.hpp: squelch_pcm16) share.
+__device__ __forceinline__ float pcm16_scale(float pk) { return pk < 1.0f ? 32767.0f : __fdiv_rn(32767.0f, pk); }
+__device__ __forceinline__ int16_t pcm16_sample(float x, float scale) { return (int16_t)(int)rounded(x * scale); }     // float -> int truncates toward zero; the writer keeps the low 16 bits
 // job = one AudioThreadInput (a block): grid = (chunks, jobs)
 CSDR_KERNEL_IO __launch_bounds__(256) void pcm16_convert(const PcmJob *__restrict__ jobs) {
     const PcmJob jb = jobs[blockIdx.y];
-    const float pk = *jb.peak;
-    const float scale = pk < 1.0f ? 32767.0f : __fdiv_rn(32767.0f, pk);
+    const float scale = pcm16_scale(*jb.peak);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < jb.n; i += 256 * gridDim.x)
-        jb.dst[i] = (int16_t)(int)rounded(jb.src[i] * scale);              // float -> int truncates toward zero; the writer keeps the low 16 bits
+        jb.dst[i] = pcm16_sample(jb.src[i], scale);
 }
 
 // ---- ingest: host block -> HBM with I and Q exchanged on the way (the reference swaps while it copies the block together).

@@ -992,6 +992,96 @@ class ScopeBank:
             self.h = C.c_void_p()
 
 
+SQUELCH_BLOCK = np.dtype([("level_accum", "<f8"), ("level_count", "<i4"), ("n_in", "<i4"), ("n_audio", "<i4"), ("audio_peak", "<f4")])     # csdr_squelch_block
+SQUELCH_ITEM = np.dtype([("level", "<f4"), ("floor", "<f4"), ("ceil", "<f4"), ("flags", "<u4")])                                      # csdr_squelch_item
+
+
+class SquelchBank:
+    """DemodulatorThread's signal level, floor, ceiling and squelch for N demodulators (csdr_squelch): every slot stepped through every block of a
+    batch in one launch; the flags gate the mixer feed (AudioMixer.push_bank_squelched) and a bank-wide PCM16 recorder (record)."""
+
+    def __init__(self, ctx, max_slots, max_blocks):
+        self._l = H.lib()
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        self.max_slots, self.max_blocks = int(max_slots), int(max_blocks)
+        H.check(self._l.csdr_squelch_create(ctx.h, self.max_slots, self.max_blocks, C.byref(self.h)))
+
+    def set_slot(self, slot, enabled=False, level_db=0.0, muted=False, record=H.CSDR_RECORD_SILENCE):
+        """squelchEnabled, squelchLevel, muted and the recorder's option; read by the next process call"""
+        H.check(self._l.csdr_squelch_set_slot(self.h, int(slot), int(bool(enabled)), float(level_db), int(bool(muted)), int(record)))
+
+    def reset_slot(self, slot):
+        H.check(self._l.csdr_squelch_reset_slot(self.h, int(slot)))
+
+    def state(self, slot):
+        """-> (signalLevel, signalFloor, signalCeil, squelchBreak) after the last process"""
+        lv, fl, ce, br = C.c_float(), C.c_float(), C.c_float(), C.c_int()
+        H.check(self._l.csdr_squelch_get_state(self.h, int(slot), C.byref(lv), C.byref(fl), C.byref(ce), C.byref(br)))
+        return np.float32(lv.value), np.float32(fl.value), np.float32(ce.value), bool(br.value)
+
+    def try_process(self, inputs):
+        """inputs: [dict(slot, sample_rate, blocks, audio=None)]; blocks: a SQUELCH_BLOCK array or rows (level_accum, level_count, n_in, n_audio,
+        audio_peak); audio: the blocks' floats back to back as a numpy array, or a DevicePointer -> the return code"""
+        arr = (H.SquelchInput * max(len(inputs), 1))()
+        keep = []
+        for k, x in enumerate(inputs):
+            blocks = np.ascontiguousarray(np.asarray(x["blocks"], dtype=SQUELCH_BLOCK) if not isinstance(x["blocks"], np.ndarray) else x["blocks"].astype(SQUELCH_BLOCK, copy=False))
+            keep.append(blocks)
+            arr[k].slot, arr[k].n_blocks, arr[k].sample_rate = int(x["slot"]), int(x.get("n_blocks", blocks.size)), int(x["sample_rate"])
+            arr[k].blocks = C.cast(blocks.ctypes.data, C.POINTER(H.SquelchBlock)) if blocks.size else None
+            audio = x.get("audio")
+            if isinstance(audio, DevicePointer):
+                arr[k].audio, arr[k].audio_is_dev = audio.ptr, 1
+                keep.append(audio)
+            elif audio is not None:
+                a = np.ascontiguousarray(audio, dtype=np.float32)
+                keep.append(a)
+                arr[k].audio = a.ctypes.data if a.size else None
+        return self._l.csdr_squelch_process(self.h, arr, len(inputs))
+
+    def process(self, inputs):
+        H.check(self.try_process(inputs))
+
+    def process_bank(self, bank):
+        """every block of the bank's last execute, read where it lies in HBM: one call, no host synchronisation"""
+        H.check(self._l.csdr_squelch_process_bank(self.h, bank.h))
+
+    def blocks(self, slot):
+        return self._l.csdr_squelch_blocks(self.h, int(slot))
+
+    def fetch(self, slot):
+        """-> the slot's items of the last process, a SQUELCH_ITEM array"""
+        out = np.empty(self.max_blocks, SQUELCH_ITEM)
+        n = C.c_int()
+        H.check(self._l.csdr_squelch_fetch(self.h, int(slot), C.cast(out.ctypes.data, C.POINTER(H.SquelchItem)), out.size, C.byref(n)))
+        return out[:n.value].copy()
+
+    def flags(self):
+        """-> uint8 [max_slots, max_blocks] of the last process (0 where nothing was stepped): one copy for the whole bank"""
+        out = np.empty((self.max_slots, self.max_blocks), np.uint8)
+        H.check(self._l.csdr_squelch_fetch_flags(self.h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def device_items(self):
+        """(device pointer, stride in items) of the items of the last process; the context's boundary stream waits for them"""
+        p, st = C.c_void_p(), C.c_int()
+        H.check(self._l.csdr_squelch_device_items(self.h, C.byref(p), C.byref(st)))
+        return p.value, st.value
+
+    def record(self, cap=1 << 24):
+        """-> (pcm int16 of every stepped slot packed in slot order, offsets int64 [max_slots + 1])"""
+        out = np.empty(int(cap), np.int16)
+        offs = np.empty(self.max_slots + 1, np.int64)
+        H.check(self._l.csdr_squelch_record(self.h, out.ctypes.data_as(C.c_void_p), out.size, offs.ctypes.data_as(C.c_void_p)))
+        return out[:offs[-1]], offs
+
+    def close(self):
+        if self.h:
+            self._l.csdr_squelch_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class AudioMixer:
     """AudioThread's mixing callback (csdr_mix): per-source block queues, rings in HBM, bit-exact mix-down."""
 
@@ -1019,6 +1109,12 @@ class AudioMixer:
         sl = np.ascontiguousarray(slots, dtype=np.int32)
         so = np.ascontiguousarray(sources if sources is not None else slots, dtype=np.int32)
         H.check(self._l.csdr_mix_push_bank(self.h, bank.h, sl.ctypes.data_as(C.c_void_p), so.ctypes.data_as(C.c_void_p), sl.size))
+
+    def push_bank_squelched(self, bank, squelch, slots, sources=None):
+        """push_bank for the blocks `squelch` (a SquelchBank whose last process was process_bank of the bank's last execute) left open"""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        so = np.ascontiguousarray(sources if sources is not None else slots, dtype=np.int32)
+        H.check(self._l.csdr_mix_push_squelched(self.h, bank.h, squelch.h, sl.ctypes.data_as(C.c_void_p), so.ctypes.data_as(C.c_void_p), sl.size))
 
     def queued(self, i):
         return self._l.csdr_mix_queued(self.h, int(i))

@@ -107,6 +107,23 @@ class ScopeBankItem(C.Structure):
     _fields_ = [("slot", C.c_int32), ("reserved", C.c_int32), ("frame", ScopeFrame)]
 
 
+CSDR_RECORD_SILENCE, CSDR_RECORD_SKIP_SILENCE, CSDR_RECORD_ALWAYS = 0, 1, 2
+CSDR_SQUELCH_SQUELCHED, CSDR_SQUELCH_BREAK, CSDR_SQUELCH_OPEN = 1, 2, 4
+
+
+class SquelchBlock(C.Structure):
+    _fields_ = [("level_accum", C.c_double), ("level_count", C.c_int32), ("n_in", C.c_int32), ("n_audio", C.c_int32), ("audio_peak", C.c_float)]
+
+
+class SquelchInput(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("n_blocks", C.c_int32), ("sample_rate", C.c_int32), ("audio_is_dev", C.c_int32),
+                ("blocks", C.POINTER(SquelchBlock)), ("audio", C.c_void_p)]
+
+
+class SquelchItem(C.Structure):
+    _fields_ = [("level", C.c_float), ("floor", C.c_float), ("ceil", C.c_float), ("flags", C.c_uint32)]
+
+
 _p, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 _pp = C.POINTER(C.c_void_p)
 
@@ -300,6 +317,19 @@ ABI = {
     "csdr_scopebank_frames": (_i, [_p, _i]),
     "csdr_scopebank_fetch": (_i, [_p, _i, _i, _i, _p, _i, C.POINTER(ScopeInfo)]),
     "csdr_scopebank_device_points": (_i, [_p, _i, _i, _pp, C.POINTER(_i), C.POINTER(_i)]),
+    "csdr_squelch_create": (_i, [_p, _i, _i, _pp]),
+    "csdr_squelch_destroy": (None, [_p]),
+    "csdr_squelch_set_slot": (_i, [_p, _i, _i, _f, _i, _i]),
+    "csdr_squelch_reset_slot": (_i, [_p, _i]),
+    "csdr_squelch_get_state": (_i, [_p, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
+    "csdr_squelch_process": (_i, [_p, C.POINTER(SquelchInput), _i]),
+    "csdr_squelch_process_bank": (_i, [_p, _p]),
+    "csdr_squelch_blocks": (_i, [_p, _i]),
+    "csdr_squelch_fetch": (_i, [_p, _i, C.POINTER(SquelchItem), _i, C.POINTER(_i)]),
+    "csdr_squelch_fetch_flags": (_i, [_p, _p, _i64]),
+    "csdr_squelch_device_items": (_i, [_p, _pp, C.POINTER(_i)]),
+    "csdr_squelch_record": (_i, [_p, _p, _i64, _p]),
+    "csdr_mix_push_squelched": (_i, [_p, _p, _p, _p, _p, _i]),
     "csdr_wfbank_create": (_i, [_p, _pp]),
     "csdr_wfbank_destroy": (None, [_p]),
     "csdr_wfbank_setup": (_i, [_p, _i, _i, _i, _i]),

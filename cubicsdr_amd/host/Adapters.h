@@ -425,6 +425,14 @@ public:
         for (auto &s : sources) idx.push_back(s ? s->index_ : -1);
         return !bankSlots.empty() && csdr_mix_push_bank(mix_, bank, bankSlots.data(), idx.data(), (int)bankSlots.size()) == CSDR_OK;
     }
+    // the same for the blocks a squelch bank left open (!squelched && !muted, DemodulatorThread.cpp:318-328): every listed demodulator, block by block;
+    // `squelch` has processed this bank's last execute (DemodSquelchBank::process, host/DemodSquelch.h)
+    bool takeBankAudioSquelched(csdr_bank *bank, csdr_squelch *squelch, const std::vector<int> &bankSlots, const std::vector<std::shared_ptr<AudioMixSource>> &sources) {
+        std::lock_guard<std::mutex> g(mu_);
+        std::vector<int> idx;
+        for (auto &s : sources) idx.push_back(s ? s->index_ : -1);
+        return !bankSlots.empty() && csdr_mix_push_squelched(mix_, bank, squelch, bankSlots.data(), idx.data(), (int)bankSlots.size()) == CSDR_OK;
+    }
     // the sound device's callback: nBufferFrames interleaved stereo frames into `out`; always 0 (the reference returns 1 only when terminated)
     int callback(float *out, unsigned int nBufferFrames) {
         std::lock_guard<std::mutex> g(mu_);

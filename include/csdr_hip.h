@@ -49,6 +49,7 @@ typedef struct csdr_distrib csdr_distrib; /* FFTDataDistributor's line cutting: 
 typedef struct csdr_specbank csdr_specbank; /* N x SpectrumVisualProcessor, one per demodulator: every slot and block of an execute in one launch */
 typedef struct csdr_wfbank csdr_wfbank;     /* N x WaterfallPanel, one per demodulator: every slot of a step, an update or a render in one launch */
 typedef struct csdr_scopebank csdr_scopebank; /* N x ScopeVisualProcessor, one per demodulator: every slot and frame of a call in two launches */
+typedef struct csdr_squelch csdr_squelch;     /* N x DemodulatorThread's level, floor, ceiling and squelch: every slot and block of an execute in one launch */
 
 /* ------------------------------------------------------------------ context */
 int         csdr_abi_version(void);
@@ -866,6 +867,90 @@ int  csdr_mix_render(csdr_mix *mix, int frames, int n_buffers, float *out_host);
  * every block with its own peak, as one AudioThreadInput each. */
 int  csdr_mix_fetch_pcm16(csdr_mix *mix, int16_t *out_host, int cap_samples, float peak, int per_buffer_peak, int *n);
 int  csdr_bank_fetch_pcm16(csdr_bank *bank, int slot, int16_t *out_host, int cap_samples, int *n);
+
+/* ------------------------------------------------------------------ Squelch bank: level gate, gated mix and recorder per demodulator
+ * DemodulatorThread::run decides per block whether anyone hears or records a demodulator's audio (src/demod/DemodulatorThread.cpp:142-238,
+ * :318-345): signalLevel, signalFloor, signalCeil, squelchBreak, and the settings squelchEnabled, squelchLevel, muted.  A csdr_squelch holds them
+ * for max_slots demodulators; the state of every slot and the items of every block stay in HBM, and one call steps every slot through every block
+ * of a batch in ONE launch (squelch_scan); two more (squelch_pack, squelch_pcm16) write the recorder's stream.  Lines are those of
+ * src/demod/DemodulatorThread.cpp unless a file is named.
+ * 1. Limits.  1 <= max_slots <= 4096 (the packing kernel is one workgroup: 16 slots per thread), max_blocks >= 1; otherwise CSDR_EINVAL.
+ * 2. Settings (csdr_squelch_set_slot): squelchEnabled (:392-397 switches it on with the level; here the caller says so), squelchLevel in dB, muted
+ *    (:339-345), and the recorder option of AudioSinkFileThread.cpp:19-44.  THEY TAKE EFFECT AT THE NEXT PROCESS CALL AND ARE CONSTANT WITHIN IT: they
+ *    are host values that travel with each call's plan.  The reference reads its atomics once per block, so a change made while a batch is in
+ *    flight lands at a block boundary inside it there and at the batch boundary here.  Defaults: off, 0 dB, not muted, CSDR_RECORD_SILENCE.
+ * 3. Per block of a slot, in block order (:142-220), the statements of host/DemodLevel.h: have_level = n_audio > 0 (:145);
+ *    currentSignalLevel = 20 log10(max(level_accum / level_count, 1e-20)) in double (:59-67); sampleTime = double(n_in) / double(sample_rate);
+ *    float trackers, updates in double, stored as float (:167-196); a block without audio still steps signalLevel towards 0 dB, which is what a
+ *    digital slot does on every block.  No special cases beyond the reference's own.
+ * 4. State.  A slot starts as the constructor leaves it (:20-27): -100, -30, 30, false.  csdr_squelch_reset_slot restores that and leaves the
+ *    settings; reconfiguring the demodulator's slot in the bank does not reset (the reference's thread outlives its modem).  csdr_squelch_get_state
+ *    reads the state after the last process: the meters (synchronises).
+ * 5. Items.  One per stepped block: level, floor, ceil after the step and flags -- bit 0 squelched (:198), bit 1 squelchBreak after the step
+ *    (:200-220; the solo-mode lock is GUI state and stays out), bit 2 open = !squelched && !muted, the condition of the audio push (:318-328).
+ * 6. csdr_squelch_process: explicit inputs, one csdr_squelch_input per slot, so that the object is usable without a csdr_bank.  `blocks` is host
+ *    memory; `audio` (optional: the recorder needs it, the level step does not) holds the blocks' floats back to back in host memory (copied inside
+ *    the call) or, with audio_is_dev, in device memory produced on the boundary stream, which must stay valid until the call's work is done.
+ *    Slots not named keep their state and report 0 blocks.
+ * 7. csdr_squelch_process_bank: the bank's last execute, read where it lies in HBM (the level sums, the peaks, the block plan, the audio).  A slot
+ *    is stepped when it is configured and active, has results in that execute, was not skipped by the shift rule (an unpushed block never reaches
+ *    DemodulatorThread) and is not front-end-only (CSDR_MODEM_HOST: its level is the plug-in's to form).  n_in = the block's n_iq, sample_rate = the
+ *    slot's bandwidth.  Digital slots step with have_level false.  Every other slot keeps its state and reports 0 blocks.  Both handles are used by
+ *    this call; slots at or above the smaller of the two slot counts are not looked at.
+ * 8. Recorder.  A slot's batch goes through AudioFileWAV's conversion (src/audio/AudioFileWAV.cpp:133-157, the rule of csdr_bank_fetch_pcm16), each
+ *    block with its own audio_peak.  CSDR_RECORD_SILENCE: squelched blocks as zeros of the same length; CSDR_RECORD_SKIP_SILENCE: squelched blocks
+ *    left out; CSDR_RECORD_ALWAYS: as if there were no squelch (AudioSinkFileThread.cpp:27-44).  `muted` does not affect the recorder.
+ *    csdr_squelch_record copies every stepped slot's PCM16, packed in slot order, and offsets[max_slots + 1] (slot s: samples offsets[s] ..
+ *    offsets[s + 1]): one small copy and one packed copy whatever the slot count.  A slot without audio records nothing.
+ * 9. csdr_mix_push_squelched is csdr_mix_push_bank for the open blocks only: one queue entry per open block, in order, with its own peak -- the
+ *    entries the host would have made with csdr_mix_push block by block.  It requires that the squelch bank's last process was
+ *    csdr_squelch_process_bank of THIS bank's last execute (anything else: CSDR_ESTATE).  The mixer's queues are host state, so the call reads the
+ *    flags once for the whole bank -- csdr_squelch_fetch_flags' copy, cached until the next process.  The all-or-nothing undo on a ring overrun
+ *    and the stop at the first full queue are csdr_mix_push_bank's.
+ * 10. Refusals are whole-call and change nothing: not created / no execute yet CSDR_ESTATE; a bank of another context CSDR_EINVAL; n_blocks above
+ *    max_blocks (or negative), a slot out of range, the same slot twice in one process, a negative n_audio or n_in, a record option outside 0 .. 2:
+ *    CSDR_EINVAL; an output capacity too small: CSDR_ERANGE.
+ * Ordering.  All work runs on a stream of the object's own; only the calls that return data to the host synchronise it.  process_bank orders itself
+ * behind the bank's modem / audio kernels by an event and leaves events that the bank's later executes wait for ON THE DEVICE before they rewrite
+ * what was read (the audio and the sums: the next execute; the block plan: the second one after).  An execute issued straight behind process_bank
+ * and csdr_squelch_record is therefore safe.  The pointer of csdr_squelch_device_items is for a consumer on the boundary stream, which is made to
+ * wait for the items; such a reader has finished before the next process of this object. */
+#define CSDR_RECORD_SILENCE      0
+#define CSDR_RECORD_SKIP_SILENCE 1
+#define CSDR_RECORD_ALWAYS       2
+#define CSDR_SQUELCH_SQUELCHED 1u   /* flag bit 0 */
+#define CSDR_SQUELCH_BREAK     2u   /* flag bit 1 */
+#define CSDR_SQUELCH_OPEN      4u   /* flag bit 2 */
+typedef struct csdr_squelch_block {
+    double  level_accum;       /* the block's magnitude sum and its term count (csdr_block_result) */
+    int32_t level_count;
+    int32_t n_in;              /* input samples of the block: sampleTime = n_in / sample_rate */
+    int32_t n_audio;           /* floats of audio the block produced; 0: no level */
+    float   audio_peak;
+} csdr_squelch_block;
+typedef struct csdr_squelch_input {
+    int32_t slot;
+    int32_t n_blocks;
+    int32_t sample_rate;
+    int32_t audio_is_dev;
+    const csdr_squelch_block *blocks;   /* host, [n_blocks] */
+    const float *audio;                 /* NULL, or sum(n_audio) floats */
+} csdr_squelch_input;
+typedef struct csdr_squelch_item { float level, floor, ceil; uint32_t flags; } csdr_squelch_item;
+CSDR_STATIC_ASSERT(sizeof(csdr_squelch_block) == 24 && sizeof(csdr_squelch_input) == 32 && sizeof(csdr_squelch_item) == 16, "squelch bank layouts");
+int  csdr_squelch_create(csdr_ctx *ctx, int max_slots, int max_blocks, csdr_squelch **out);
+void csdr_squelch_destroy(csdr_squelch *sq);
+int  csdr_squelch_set_slot(csdr_squelch *sq, int slot, int enabled, float level_db, int muted, int record_option);
+int  csdr_squelch_reset_slot(csdr_squelch *sq, int slot);                                      /* ctor :20-27 */
+int  csdr_squelch_get_state(csdr_squelch *sq, int slot, float *level, float *floor, float *ceil, int *squelch_break);
+int  csdr_squelch_process(csdr_squelch *sq, const csdr_squelch_input *in, int n);
+int  csdr_squelch_process_bank(csdr_squelch *sq, csdr_bank *bank);                             /* both handles are used by this call */
+int  csdr_squelch_blocks(const csdr_squelch *sq, int slot);                                    /* blocks stepped by the last process */
+int  csdr_squelch_fetch(csdr_squelch *sq, int slot, csdr_squelch_item *out, int cap, int *n);
+int  csdr_squelch_fetch_flags(csdr_squelch *sq, uint8_t *out, int64_t cap_bytes);              /* [max_slots][max_blocks], 0 where nothing was stepped */
+int  csdr_squelch_device_items(csdr_squelch *sq, const csdr_squelch_item **dev, int *stride_items);   /* slot s, block b: dev[s * stride_items + b] */
+int  csdr_squelch_record(csdr_squelch *sq, int16_t *out_host, int64_t cap_samples, int64_t *offsets /* [max_slots + 1] */);
+int  csdr_mix_push_squelched(csdr_mix *mix, csdr_bank *bank, csdr_squelch *sq, const int *slots, const int *sources, int n);
 
 /* ------------------------------------------------------------------ ingest
  * The reference's reader fills pooled SDRThreadIQData blocks (SoapySDRThread.cpp:221-225) and SDRPostThread hands ONE buffer to the
