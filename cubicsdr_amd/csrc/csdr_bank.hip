@@ -34,20 +34,6 @@ static int bank_arm_bank(csdr_bank *b, const design::MsresampPlan &p, int *idx) 
     return CSDR_OK;
 }
 
-static void fill_resamp_cfg(ResampCfg &rc, const design::MsresampPlan &p, int arms_idx) {
-    memset(&rc, 0, sizeof rc);
-    rc.interp = p.interp ? 1 : 0;
-    rc.S = (int)p.S;
-    rc.step = p.step;
-    rc.arms_idx = arms_idx;
-    for (unsigned e = 0; e < p.S; ++e) {
-        // execution order: decimator runs design index S-1 first; interpolator runs design index 0 first
-        const unsigned g = p.interp ? e : (p.S - 1 - e);
-        rc.m_x[e] = (int)p.m[g];
-        for (unsigned j = 0; j < p.m[g]; ++j) rc.h_x[e][j] = p.h1[g][j];
-    }
-}
-
 extern "C" int csdr_bank_create(csdr_ctx *ctx, int max_demods, int max_blocks, csdr_bank **out) {
     DeviceScope dev__(ctx);
     if (!ctx || !out || max_demods <= 0 || max_blocks <= 0) return fail(CSDR_EINVAL, "bad argument");

@@ -149,7 +149,8 @@ static const char *kKernelNames[KID_COUNT] = {
     "specbank_process",
     "wfb_quantize", "wfb_update", "wfb_view_linear", "wfb_view_peak",
     "scopebank_wave", "scopebank_spectrum",
-    "squelch_scan", "squelch_pack", "squelch_pcm16"};
+    "squelch_scan", "squelch_pack", "squelch_pcm16",
+    "viewbank_process"};
 static int prof_drain(csdr_ctx *c) {
     if (int rc = c->sync_all()) return rc;
     std::lock_guard<std::mutex> lk(c->prof_mu);

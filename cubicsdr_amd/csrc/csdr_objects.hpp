@@ -86,6 +86,20 @@ struct SlotHost {
     int last_ash = -1;                       // floats per audio-arbitrary output of the last execute = 2^last_ash; -1: no audio stage ran
     std::shared_ptr<DigSlot> dig;           // CSDR_MODEM_DIGITAL: the decision stage behind the front-end
 };
+// a designed msresamp as the kernels read it (the demodulator bank's slots; the view bank's resamplers)
+static inline void fill_resamp_cfg(ResampCfg &rc, const design::MsresampPlan &p, int arms_idx) {
+    memset(&rc, 0, sizeof rc);
+    rc.interp = p.interp ? 1 : 0;
+    rc.S = (int)p.S;
+    rc.step = p.step;
+    rc.arms_idx = arms_idx;
+    for (unsigned e = 0; e < p.S; ++e) {
+        // execution order: decimator runs design index S-1 first; interpolator runs design index 0 first
+        const unsigned g = p.interp ? e : (p.S - 1 - e);
+        rc.m_x[e] = (int)p.m[g];
+        for (unsigned j = 0; j < p.m[g]; ++j) rc.h_x[e][j] = p.h1[g][j];
+    }
+}
 constexpr int kStageRing = 4;                // pinned staging sets for the per-batch uploads
 }  // namespace csdr
 

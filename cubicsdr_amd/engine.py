@@ -570,6 +570,117 @@ class SpectrumBank:
             self.h = C.c_void_p()
 
 
+class ViewBank:
+    """N independent SpectrumVisualProcessors in zoomed view, of one fft_size (csdr_viewbank): the reference's demodulator spectrum -- the channel
+    row shifted, resampled to rate / 2^k and shown over `bandwidth` -- for every demodulator at once; all slots and all inputs of a call in one
+    launch, state and points stay in HBM."""
+
+    def __init__(self, ctx, fft_size, max_slots, max_frames=1, max_samples=65536):
+        self._l = H.lib()
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        H.check(self._l.csdr_viewbank_create(ctx.h, C.byref(self.h)))
+        self.setup(fft_size, max_slots, max_frames, max_samples)
+
+    def setup(self, fft_size, max_slots, max_frames=1, max_samples=65536):
+        H.check(self._l.csdr_viewbank_setup(self.h, int(fft_size), int(max_slots), int(max_frames), int(max_samples)))
+        self.fft_size, self.max_slots, self.max_frames, self.max_samples = int(fft_size), int(max_slots), int(max_frames), int(max_samples)
+
+    def set_average_rate(self, r):
+        H.check(self._l.csdr_viewbank_set_average_rate(self.h, float(r)))
+
+    def set_scale_factor(self, f):
+        H.check(self._l.csdr_viewbank_set_scale_factor(self.h, float(f)))
+
+    def set_peak_hold(self, enabled):
+        H.check(self._l.csdr_viewbank_set_peak_hold(self.h, int(bool(enabled))))
+
+    def get_peak_hold(self):
+        return bool(self._l.csdr_viewbank_get_peak_hold(self.h))
+
+    def set_hide_dc(self, enabled):
+        H.check(self._l.csdr_viewbank_set_hide_dc(self.h, int(bool(enabled))))
+
+    def try_set_view(self, slot, center_freq, bandwidth):
+        return self._l.csdr_viewbank_set_view(self.h, int(slot), int(center_freq), int(bandwidth))
+
+    def set_view(self, slot, center_freq, bandwidth):
+        H.check(self.try_set_view(slot, center_freq, bandwidth))
+
+    def reset_slot(self, slot):
+        H.check(self._l.csdr_viewbank_reset_slot(self.h, int(slot)))
+
+    def try_process(self, items):
+        """items: [(slot, iq, frequency, sample_rate)] with iq a numpy array, a CUDA torch tensor, a DevicePointer, or None / empty for no
+        input -> the return code"""
+        arr = (H.ViewBankItem * max(len(items), 1))()
+        keep = []
+        for k, (slot, iq, frequency, sample_rate) in enumerate(items):
+            arr[k].slot, arr[k].frequency, arr[k].sample_rate = int(slot), int(frequency), int(sample_rate)
+            if iq is None or (isinstance(iq, np.ndarray) and iq.size == 0):
+                arr[k].n, arr[k].iq, arr[k].is_dev = 0, None, 0
+                continue
+            p, is_dev, n, ka = _as_iq_arg(iq)
+            arr[k].n, arr[k].iq, arr[k].is_dev = int(n), p.value, int(is_dev)
+            keep.append(ka)
+        rc = self._l.csdr_viewbank_process(self.h, arr, len(items))
+        self._keep = keep
+        return rc
+
+    def process(self, items):
+        H.check(self.try_process(items))
+
+    def try_process_post(self, post, slots, channels):
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        c = np.ascontiguousarray(channels, dtype=np.int32)
+        if s.size != c.size:
+            raise ValueError("%d slots, %d channels" % (s.size, c.size))
+        return self._l.csdr_viewbank_process_post(self.h, post.h, s.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), s.size)
+
+    def process_post(self, post, slots, channels):
+        """slot slots[i] gets every block of row channels[i] of the post's last execute, where it lies in HBM: one call, no host synchronisation"""
+        H.check(self.try_process_post(post, slots, channels))
+
+    def frames(self, slot):
+        return self._l.csdr_viewbank_frames(self.h, int(slot))
+
+    def fetch(self, slot, frame):
+        pts = np.empty(2 * self.fft_size, np.float32)
+        ce, fl = C.c_double(), C.c_double()
+        H.check(self._l.csdr_viewbank_fetch(self.h, int(slot), int(frame), pts.ctypes.data_as(C.c_void_p), pts.size, C.byref(ce), C.byref(fl)))
+        return pts, ce.value, fl.value
+
+    def fetch_hold(self, slot, frame):
+        """spectrum_hold_points of a frame, or None when it carries none"""
+        pts = np.empty(2 * self.fft_size, np.float32)
+        n = C.c_int()
+        H.check(self._l.csdr_viewbank_fetch_hold(self.h, int(slot), int(frame), pts.ctypes.data_as(C.c_void_p), pts.size, C.byref(n)))
+        return pts if n.value else None
+
+    def device_points(self, slot):
+        """(device pointer, frames): the [frames, fft_size] y values of the slot's last call; the context's boundary stream waits for them"""
+        p, n = C.c_void_p(), C.c_int()
+        H.check(self._l.csdr_viewbank_device_points(self.h, int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def slot_info(self, slot):
+        """-> dict of the slot's integers behind its last item (csdr_viewbank_slot_state)"""
+        st = H.ViewBankSlotState()
+        H.check(self._l.csdr_viewbank_slot_info(self.h, int(slot), C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in H.ViewBankSlotState._fields_}
+
+    def fetch_last(self, slot):
+        """the slot's fftLastData: 2 * fft_size complex samples"""
+        out = np.empty(2 * self.fft_size, np.complex64)
+        H.check(self._l.csdr_viewbank_fetch_last(self.h, int(slot), out.ctypes.data_as(C.c_void_p), 2 * out.size))
+        return out
+
+    def close(self):
+        if self.h:
+            self._l.csdr_viewbank_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 def design_gradient(stops, length=256):
     """Gradient::generate(length) for colour stops [[r, g, b], ...] (host only) -> (r, g, b) float32 arrays"""
     a = np.ascontiguousarray(stops, dtype=np.float32).reshape(-1, 3)

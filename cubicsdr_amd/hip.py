@@ -85,6 +85,16 @@ class SpecBankItem(C.Structure):
     _fields_ = [("slot", C.c_int32), ("n", C.c_int32), ("iq", C.c_void_p), ("is_dev", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ViewBankItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("n", C.c_int32), ("iq", C.c_void_p), ("is_dev", C.c_int32), ("reserved", C.c_int32),
+                ("frequency", C.c_int64), ("sample_rate", C.c_int64)]
+
+
+class ViewBankSlotState(C.Structure):
+    _fields_ = [("resample_bw", C.c_int64), ("shift_frequency", C.c_int64), ("desired_input_size", C.c_int32), ("last_data_size", C.c_int32),
+                ("peak_reset", C.c_int32), ("num_written", C.c_int32)]
+
+
 class WfBankItem(C.Structure):
     _fields_ = [("slot", C.c_int32), ("n_floats_per_line", C.c_int32), ("points", C.c_void_p), ("is_dev", C.c_int32), ("n_lines", C.c_int32)]
 
@@ -305,6 +315,24 @@ ABI = {
     "csdr_specbank_fetch": (_i, [_p, _i, _i, _p, _i, C.POINTER(_d), C.POINTER(_d)]),
     "csdr_specbank_fetch_hold": (_i, [_p, _i, _i, _p, _i, C.POINTER(_i)]),
     "csdr_specbank_device_points": (_i, [_p, _i, _pp, C.POINTER(_i)]),
+    "csdr_viewbank_create": (_i, [_p, _pp]),
+    "csdr_viewbank_destroy": (None, [_p]),
+    "csdr_viewbank_setup": (_i, [_p, _i, _i, _i, _i]),
+    "csdr_viewbank_set_average_rate": (_i, [_p, _f]),
+    "csdr_viewbank_set_scale_factor": (_i, [_p, _f]),
+    "csdr_viewbank_set_peak_hold": (_i, [_p, _i]),
+    "csdr_viewbank_get_peak_hold": (_i, [_p]),
+    "csdr_viewbank_set_hide_dc": (_i, [_p, _i]),
+    "csdr_viewbank_set_view": (_i, [_p, _i, C.c_int64, C.c_int64]),
+    "csdr_viewbank_reset_slot": (_i, [_p, _i]),
+    "csdr_viewbank_process": (_i, [_p, C.POINTER(ViewBankItem), _i]),
+    "csdr_viewbank_process_post": (_i, [_p, _p, _p, _p, _i]),
+    "csdr_viewbank_frames": (_i, [_p, _i]),
+    "csdr_viewbank_fetch": (_i, [_p, _i, _i, _p, _i, C.POINTER(_d), C.POINTER(_d)]),
+    "csdr_viewbank_fetch_hold": (_i, [_p, _i, _i, _p, _i, C.POINTER(_i)]),
+    "csdr_viewbank_device_points": (_i, [_p, _i, _pp, C.POINTER(_i)]),
+    "csdr_viewbank_slot_info": (_i, [_p, _i, C.POINTER(ViewBankSlotState)]),
+    "csdr_viewbank_fetch_last": (_i, [_p, _i, _p, _i]),
     "csdr_scopebank_create": (_i, [_p, _pp]),
     "csdr_scopebank_destroy": (None, [_p]),
     "csdr_scopebank_setup": (_i, [_p, _i, _i, _i, _i]),

@@ -50,6 +50,7 @@ typedef struct csdr_specbank csdr_specbank; /* N x SpectrumVisualProcessor, one 
 typedef struct csdr_wfbank csdr_wfbank;     /* N x WaterfallPanel, one per demodulator: every slot of a step, an update or a render in one launch */
 typedef struct csdr_scopebank csdr_scopebank; /* N x ScopeVisualProcessor, one per demodulator: every slot and frame of a call in two launches */
 typedef struct csdr_squelch csdr_squelch;     /* N x DemodulatorThread's level, floor, ceiling and squelch: every slot and block of an execute in one launch */
+typedef struct csdr_viewbank csdr_viewbank;   /* N x SpectrumVisualProcessor in zoomed view, one per demodulator: every slot and input of a call in one launch */
 
 /* ------------------------------------------------------------------ context */
 int         csdr_abi_version(void);
@@ -673,7 +674,8 @@ int  csdr_spec_process_distrib(csdr_spec *spec, csdr_distrib *d);
  *    average rate, scale factor and peak-hold setting stay).  Slots are independent: what one slot is fed, and whether others are fed at all,
  *    changes no bit of another slot's output; items of one slot are its inputs in the order given, whatever lies between them.
  * 6. Not in this object, and refused or absent rather than approximated: the zoomed view (the reference's demodulator view zooms the CHANNEL row;
- *    this bank shows the demodulator's own band at its own rate), hideDC, sizes that are not powers of two, F > 2048.
+ *    this bank shows the demodulator's own band at its own rate), hideDC, sizes that are not powers of two, F > 2048.  The zoomed view per slot,
+ *    with hideDC, is an object of its own: csdr_viewbank ("View bank" below).
  * Ordering.  All work runs on a stream of the object's own, as a waterfall's does; the fetches synchronise it.  Host inputs are staged with
  * hipMemcpyAsync (the rule of csdr_post_execute for page-locked memory holds); device inputs must have been produced on the boundary stream.
  * csdr_specbank_process_bank orders itself behind the bank's front-end by an event and leaves one that the bank's later executes wait for before
@@ -951,6 +953,97 @@ int  csdr_squelch_fetch_flags(csdr_squelch *sq, uint8_t *out, int64_t cap_bytes)
 int  csdr_squelch_device_items(csdr_squelch *sq, const csdr_squelch_item **dev, int *stride_items);   /* slot s, block b: dev[s * stride_items + b] */
 int  csdr_squelch_record(csdr_squelch *sq, int16_t *out_host, int64_t cap_samples, int64_t *offsets /* [max_slots + 1] */);
 int  csdr_mix_push_squelched(csdr_mix *mix, csdr_bank *bank, csdr_squelch *sq, const int *slots, const int *sources, int n);
+
+/* ------------------------------------------------------------------ View bank: the zoomed demodulator spectrum, one per demodulator
+ * The reference's demodulator spectrum and waterfall are a zoomed view of the CHANNEL row: SDRPostThread pushes the active demodulator's channel
+ * row, at the channel's centre and rate, into IQActiveDemodVisualDataOutput (SDRPostThread.cpp:289-291, :334, :386) and AppFrame keeps
+ * getDemodSpectrumProcessor() in setView(true, centre, bandwidth) (AppFrame.cpp:785-792, :2317-2320).  A csdr_viewbank holds max_slots such
+ * processors, all of one fft_size F (Fi = 2 F); state and points stay in HBM, and one call runs all slots and all inputs it is given in ONE kernel
+ * launch.  Every slot behaves as one SpectrumVisualProcessor after setup(F) on which setView(true, centre, bandwidth) was called before its first
+ * input, and which receives one process() input per item.  Lines are those of src/process/SpectrumVisualProcessor.cpp.
+ * 1. Limits.  F is a power of two, 8 <= F <= 2048; 1 <= max_slots <= 4096; max_frames >= 1 frames per slot and call; max_samples >= 1 is the longest
+ *    input.  Bad counts: CSDR_EINVAL; an F from 8 on that is not a power of two or exceeds 2048: CSDR_EUNSUPPORTED.  A view that needs more than 10
+ *    half-band stages (resampleBw below rate / 1024), or one wider than 32 input rates (more than 64 bins per display point): CSDR_EUNSUPPORTED for
+ *    that call.  An input longer than max_samples, or more than max_frames frames for a slot: CSDR_ERANGE for the whole call.  A negative sample
+ *    rate: CSDR_EINVAL.  A refusal enqueues nothing and changes no state, neither on the host nor on the device.
+ * 2. Per item {slot, n, iq, is_dev, frequency, sample_rate}, planned on the host from these integers alone -- no decision depends on a sample value.
+ *    The head of process(): doPeak is taken before the countdown moves, the peak reset is enqueued in front of the item (:247, :264-273).
+ *    sample_rate == 0 ends the input there (:284-287).  resampleBw comes from repeated long division by 2 while resampleBw / 2 >= bandwidth
+ *    (:289-291; 503606 becomes 251803, then 125901: the truncation is kept); resamplerRatio is the double quotient (:293);
+ *    desiredInputSize = (size_t)(Fi / ratio), clamped to n (:295-302): only that prefix of the input is consumed -- the oscillator advances by it and
+ *    the resampler sees the concatenation of these prefixes.  Retune (:304-336), when centerFreq != frequency and the shift or the input rate changed:
+ *    in range -- |frequency - centre| < sample_rate / 2, the application rate being the input's, as csdr_spec defines it -- shiftFrequency is adopted,
+ *    the oscillator's increment becomes the phase word of (float)(2 pi |shift| / rate), and fft_result_ma / _maa move by
+ *    numShift = floor(|freqDiff| / (lastBandwidth / Fi)) bins, left for a positive freqDiff, when 0 < numShift < Fi / 2 (the peak arrays do not
+ *    move); peakReset = 30 is set whether or not the range test passed; out of range the old shift and increment keep mixing.  Mixing is up for
+ *    shiftFrequency < 0, else down (:345-349); none, and no advance of the oscillator, when centerFreq == frequency (:351).  The resampler is
+ *    rebuilt when there is none or resampleBw or the input rate changed (:354-368): msresamp_crcf_create((float)ratio, 60), every window empty,
+ *    phase and buffer index 0, the oscillator's phase lives on; bwDiff, lastBandwidth, lastInputBandwidth and peakReset = 30 are set.
+ *    num_written is that resampler's output count for the consumed samples, in closed form.  Then the frame rule of :399-421 on num_written,
+ *    exactly as "Spectrum bank" item 2 states it, late-priming quirk included (an input whose num_written is 0 primes, or slides by nothing, as
+ *    the rule says).  The stretch / squeeze of the averagers (:454-492) runs in front of the averaging of a frame when the resampler is new and the
+ *    slot's previous input was a view input: squeeze (src = Fi/4 + i/2) for bwDiff < 0, else stretch (inside [Fi/4, Fi - Fi/4) take (i - Fi/4) 2,
+ *    elsewhere 0).  last_view becomes true after every non-empty item, the early returns included.
+ * 3. Per frame: the statements of "Spectrum bank" item 3, with two differences.  The display walks the view map of :532-560: the double accumulator
+ *    is stepped by 2 bandwidth / resampleBw per point, idx = round(visualStart + i) as unsigned; a visited bin with 0 < idx < Fi contributes
+ *    fft_result_maa[idx], any other fft_floor_maa; the sum is divided by the count and log10 is taken in double.  The host computes the map per slot
+ *    and uploads it only when (bandwidth, resampleBw) changed.  The hold points walk the same map over fft_result_peak.  hideDC (:578-623, the
+ *    reference's integer arithmetic) is a per-object setter and is applied BY THE KERNEL to points and hold points: what lies in HBM is what the
+ *    reference hands its canvases.
+ * 4. The library's own definitions.  An item with n = 0 is no input at all.  csdr_viewbank_set_view with bandwidth <= 0 is CSDR_EINVAL; a slot that
+ *    was never given a view is refused with CSDR_ESTATE when fed.  csdr_viewbank_reset_slot makes a fresh processor on which setPeakHold(the
+ *    object's setting) and the slot's last setView were called; csdr_viewbank_setup makes every slot a processor without a view.  Slots share
+ *    nothing: what one slot is fed changes no bit of another's output; however a slot's inputs are cut into calls, its output is the same bits.
+ * Ordering.  All work runs on a stream of the object's own; the fetches synchronise it.  Host inputs are staged with hipMemcpyAsync; device inputs
+ * must have been produced on the boundary stream.  csdr_viewbank_process_post waits on its stream for the channelizer batch's event and leaves one
+ * of the batch's reader events behind its kernel: neither object synchronises the host for the other, and the post rotates its output buffers from
+ * then on.  The points are rewritten by the next process call; a reader of csdr_viewbank_device_points' pointer must have FINISHED before it. */
+typedef struct csdr_viewbank_item {
+    int32_t slot;              /* 0 .. max_slots - 1 */
+    int32_t n;                 /* complex samples of this process() input; 0: no input */
+    const float *iq;           /* interleaved (re, im); device memory (8-byte aligned) when is_dev != 0 */
+    int32_t is_dev;
+    int32_t reserved;
+    int64_t frequency;         /* the input's centre frequency (SpectrumVisualData::frequency) */
+    int64_t sample_rate;       /* the input's sample rate (::sampleRate) */
+} csdr_viewbank_item;
+CSDR_STATIC_ASSERT(sizeof(csdr_viewbank_item) == 40 && offsetof(csdr_viewbank_item, iq) == 8 && offsetof(csdr_viewbank_item, frequency) == 24, "csdr_viewbank_item layout");
+typedef struct csdr_viewbank_slot_state {      /* a slot's integers behind its last item */
+    int64_t resample_bw;       /* resampleBw */
+    int64_t shift_frequency;   /* shiftFrequency */
+    int32_t desired_input_size;/* desiredInputSize (before the clamp to n) */
+    int32_t last_data_size;    /* lastDataSize */
+    int32_t peak_reset;        /* peakReset */
+    int32_t num_written;       /* num_written of the last item */
+} csdr_viewbank_slot_state;
+CSDR_STATIC_ASSERT(sizeof(csdr_viewbank_slot_state) == 32, "csdr_viewbank_slot_state layout");
+int  csdr_viewbank_create(csdr_ctx *ctx, csdr_viewbank **out);
+void csdr_viewbank_destroy(csdr_viewbank *vb);
+int  csdr_viewbank_setup(csdr_viewbank *vb, int fft_size, int max_slots, int max_frames, int max_samples);
+int  csdr_viewbank_set_average_rate(csdr_viewbank *vb, float rate);       /* setFFTAverageRate */
+int  csdr_viewbank_set_scale_factor(csdr_viewbank *vb, float sf);         /* setScaleFactor */
+int  csdr_viewbank_set_peak_hold(csdr_viewbank *vb, int enabled);         /* setPeakHold :115-125, on every slot */
+int  csdr_viewbank_get_peak_hold(const csdr_viewbank *vb);
+int  csdr_viewbank_set_hide_dc(csdr_viewbank *vb, int enabled);           /* setHideDC :204-209, on every slot */
+int  csdr_viewbank_set_view(csdr_viewbank *vb, int slot, int64_t center_freq, int64_t bandwidth);     /* setView(true, ...) :64-72 */
+int  csdr_viewbank_reset_slot(csdr_viewbank *vb, int slot);
+/* n_items process() inputs; the items of one slot are its inputs in the order given */
+int  csdr_viewbank_process(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_items);
+/* After a csdr_post_execute (CSDR_ESTATE before the first): slot slots[i] gets one item per block of that execute -- that block of row channels[i]
+ * where it lies in the post's buffer, stamped with the centre and csdr_post_channel_rate that csdr_bank_execute uses for that row.  CSDR_ERANGE when
+ * the batch already has its four readers; CSDR_EINVAL for a post of another context, a packed-row producer, a row the channelizer does not
+ * produce.  No host synchronisation in either direction.  Both handles are used by this call. */
+int  csdr_viewbank_process_post(csdr_viewbank *vb, csdr_post *post, const int *slots, const int *channels, int n);
+int  csdr_viewbank_frames(const csdr_viewbank *vb, int slot);             /* frames the last process call produced for the slot */
+/* SpectrumVisualData of frame `frame` of the slot: spectrum_points[2 F] = (x, y) pairs, fft_ceiling, fft_floor (either may be NULL) */
+int  csdr_viewbank_fetch(csdr_viewbank *vb, int slot, int frame, float *points_host, int cap_floats, double *fft_ceiling, double *fft_floor);
+int  csdr_viewbank_fetch_hold(csdr_viewbank *vb, int slot, int frame, float *hold_host, int cap_floats, int *n_floats);
+/* the y values of the slot's frames of the last call, [frames][F] floats in HBM: the boundary stream is made to wait for them.  The pointer
+ * csdr_wfbank_step / csdr_waterfall_step take with is_dev = 1. */
+int  csdr_viewbank_device_points(csdr_viewbank *vb, int slot, const float **dev, int *frames);
+int  csdr_viewbank_slot_info(const csdr_viewbank *vb, int slot, csdr_viewbank_slot_state *out);
+/* the slot's fftLastData, 2 Fi floats (synchronises): the resampler's samples as the frame rule arranged them */
+int  csdr_viewbank_fetch_last(csdr_viewbank *vb, int slot, float *out, int cap_floats);
 
 /* ------------------------------------------------------------------ ingest
  * The reference's reader fills pooled SDRThreadIQData blocks (SoapySDRThread.cpp:221-225) and SDRPostThread hands ONE buffer to the
