@@ -54,10 +54,7 @@ extern "C" int csdr_scope_setup(csdr_scope *s, int fft_size, int max_frames, int
     if (int rc = s->ctx->sync_all()) return rc;
     s->ready = false;
     s->L = fft_size; s->max_frames = max_frames; s->max_n = max_samples;
-    std::vector<float2> t(kTwTab);
-    for (int i = 0; i < kTwTab; i++) { const double a = -2.0 * M_PI * i / kTwTab; t[i] = make_float2((float)std::cos(a), (float)std::sin(a)); }
-    if (int rc = s->tw4096.reserve(kTwTab)) return rc;
-    CSDR_HIP_TRY(hipMemcpy(s->tw4096.p, t.data(), kTwTab * sizeof(float2), hipMemcpyHostToDevice));
+    if (int rc = upload_twiddles(s->tw4096, kTwTab)) return rc;
     const size_t H = (size_t)fft_size / 2;
     if (int rc = s->ma.reserve(H)) return rc;
     if (int rc = s->maa.reserve(H)) return rc;

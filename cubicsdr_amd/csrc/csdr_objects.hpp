@@ -1,6 +1,7 @@
 // csdr_objects.hpp -- the object layouts behind the opaque handles of include/csdr_hip.h that more than one translation unit looks into
 // (the demodulator bank reads the channelizer's output rotation; the audio / scope edges read the bank's slots).
 #pragma once
+#include <cmath>
 #include <map>
 #include <memory>
 #include <vector>
@@ -99,6 +100,15 @@ static inline void fill_resamp_cfg(ResampCfg &rc, const design::MsresampPlan &p,
         rc.m_x[e] = (int)p.m[g];
         for (unsigned j = 0; j < p.m[g]; ++j) rc.h_x[e][j] = p.h1[g][j];
     }
+}
+// the base twiddle table exp(-2 pi i k / n) that lds_fft and the spectrum chain read (n = kTwTab of kernels_spec.hpp), on the device once per object
+static inline int upload_twiddles(DevBuf<float2> &tw, int n) {
+    if (tw.p) return CSDR_OK;
+    std::vector<float2> t((size_t)n);
+    for (int i = 0; i < n; i++) { const double a = -2.0 * M_PI * i / n; t[(size_t)i] = make_float2((float)std::cos(a), (float)std::sin(a)); }
+    if (int rc = tw.reserve((size_t)n)) return rc;
+    CSDR_HIP_TRY(hipMemcpy(tw.p, t.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice));
+    return CSDR_OK;
 }
 constexpr int kStageRing = 4;                // pinned staging sets for the per-batch uploads
 }  // namespace csdr

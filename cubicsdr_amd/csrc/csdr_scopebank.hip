@@ -88,12 +88,7 @@ extern "C" int csdr_scopebank_setup(csdr_scopebank *sb, int fft_size, int max_sl
     CSDR_HIP_TRY(hipStreamSynchronize(sb->st));
     sb->ready = false;
     const size_t H = (size_t)fft_size / 2, S = (size_t)max_slots, SF = S * (size_t)max_frames;
-    if (!sb->tw4096.p) {
-        std::vector<float2> t(kTwTab);
-        for (int i = 0; i < kTwTab; i++) { const double a = -2.0 * M_PI * i / kTwTab; t[(size_t)i] = make_float2((float)std::cos(a), (float)std::sin(a)); }
-        if (int rc = sb->tw4096.reserve(kTwTab)) return rc;
-        CSDR_HIP_TRY(hipMemcpy(sb->tw4096.p, t.data(), kTwTab * sizeof(float2), hipMemcpyHostToDevice));
-    }
+    if (int rc = upload_twiddles(sb->tw4096, kTwTab)) return rc;
     if (int rc = sb->ma.reserve(S * H)) return rc;
     if (int rc = sb->maa.reserve(S * H)) return rc;
     if (int rc = sb->trk.reserve(S)) return rc;

@@ -206,10 +206,7 @@ extern "C" int csdr_spec_setup(csdr_spec *s, int fft_size, int max_frames) {
     }
     g.lgRa = ilog2(g.Ra); g.lgRb = ilog2(g.Rb);
     s->max_frames = max_frames;
-    std::vector<float2> t(kTwTab);
-    for (int i = 0; i < kTwTab; i++) { double a = -2.0 * M_PI * i / kTwTab; t[i] = make_float2((float)std::cos(a), (float)std::sin(a)); }
-    if (int rc = s->tw4096.reserve(kTwTab)) return rc;
-    CSDR_HIP_TRY(hipMemcpy(s->tw4096.p, t.data(), kTwTab * sizeof(float2), hipMemcpyHostToDevice));
+    if (int rc = upload_twiddles(s->tw4096, kTwTab)) return rc;
     std::vector<float2> lo(1024), hi(std::max(1, N / 1024));
     for (int i = 0; i < 1024; i++) { double a = -2.0 * M_PI * i / N; lo[i] = make_float2((float)std::cos(a), (float)std::sin(a)); }
     for (size_t i = 0; i < hi.size(); i++) { double a = -2.0 * M_PI * (double)(i * 1024) / N; hi[i] = make_float2((float)std::cos(a), (float)std::sin(a)); }

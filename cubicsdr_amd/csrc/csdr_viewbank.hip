@@ -4,6 +4,8 @@
 // and how far the averagers move, whether the resampler is rebuilt, num_written in closed form (design::resamp_count), the branch of the frame rule,
 // where the peak-hold countdown stands.  ONE launch of viewbank_process (kernels_viewbank.hpp) does the arithmetic of all slots and all inputs of a
 // call.  All work runs on a stream of the object's own; a channelizer's rows are reached through its batch events (csdr_viewbank_process_post).
+// The frame store, the countdown, the frame rule, the slot order of a call and the fetches are specbank_host.hpp's, shared with csdr_specbank.hip;
+// this unit states the view plan, the resamplers and maps, and where the inputs come from.
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -11,7 +13,7 @@
 #include <vector>
 
 #define CSDR_TU_VIEWBANK 1     // this unit is the home of its kernel (kernels_viewbank.hpp)
-#include "csdr_objects.hpp"
+#include "specbank_host.hpp"
 #include "kernels_viewbank.hpp"
 
 using namespace csdr;
@@ -20,14 +22,11 @@ static_assert(sizeof(csdr_viewbank_item) == 40 && offsetof(csdr_viewbank_item, i
 static_assert(sizeof(csdr_viewbank_slot_state) == 32, "csdr_viewbank_slot_state layout");
 
 namespace {
-struct VbSlot {
+struct VbSlot : SbSlot {
     // setView (:64-72): survives csdr_viewbank_reset_slot
     bool has_view = false;
     int64_t centre = 0, bandwidth = 0;
-    // the processor's integers
-    int last_size = 0;                   // lastDataSize
-    int peak_reset = 0;                  // peakReset
-    int frames = 0;                      // frames of the last call
+    // the processor's integers (lastDataSize, peakReset and the frames of the last call: SbSlot)
     long long last_bandwidth = 0, last_input_bandwidth = 0, shift_frequency = 0;
     bool have_resampler = false, last_view = false;
     int cfg = -1;                        // the resampler in force (csdr_viewbank::cfgs_h)
@@ -39,29 +38,15 @@ struct VbSlot {
     int desired_input_size = 0, num_written = 0;
     int64_t resample_bw = 0;
 };
-constexpr int kVbPeakResetCount = 30;        // PEAK_RESET_COUNT (SpectrumVisualProcessor.h:12)
-constexpr int kVbStage = 2;                  // page-locked staging sets of the plan
 constexpr double kVbMaxBinsPerPoint = 64.0;  // a view wider than 32 input rates walks more bins per point than this: refused
 }  // namespace
 
-struct csdr_viewbank {
-    csdr_ctx *ctx = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;      // boundary stream / channelizer -> st, st -> boundary stream (csdr_viewbank_device_points)
-    bool ready = false;
-    int F = 0, Fi = 0, max_slots = 0, max_frames = 0, max_samples = 0;
-    float avg_rate = 0.65f, sf = 1.0f, sf_last = 1.0f;
-    bool peak_hold = false, hide_dc = false;
-    std::vector<VbSlot> slots;
-    std::vector<int> touched;                          // slots that got frames in the last call
-    DevBuf<float2> tw4096, last, stage, rs, y;
-    DevBuf<double> ma, maa, peak;
-    DevBuf<SpecBankTrk> trk;
-    DevBuf<float> points, hold;
-    DevBuf<SpecBankFrame> meta;
+struct csdr_viewbank : SbBank<VbSlot, ViewBankJob> {
+    static constexpr const char *kName = "view bank";
+    int max_samples = 0;
+    bool hide_dc = false;
+    DevBuf<float2> rs, y;
     DevBuf<int2> maps, maps_call;                      // [slots][F] the slots' view maps; the maps a call brings, until they are the slots'
-    StageRing<kVbStage> plan;                          // SpecBankRun [runs] | ViewBankJob [jobs] of the call being run
-    SpecBankTrk trk0{};
     // the resamplers designed so far, by the bit pattern of (float)resamplerRatio: a handful per input rate (resampleBw = rate / 2^k)
     std::map<uint32_t, int> cfg_index;
     std::vector<ResampCfg> cfgs_h;
@@ -71,9 +56,7 @@ struct csdr_viewbank {
     size_t cfgs_on_device = 0;
     size_t lds_attr = 0;
     // scratch of a call's planning
-    std::vector<VbSlot> work;
-    std::vector<int> n_jobs_of, job_at, cursor, run_slots, job_map;
-    std::vector<ViewBankJob> jobs_h;
+    std::vector<int> job_map;
     std::vector<std::pair<int, std::vector<int2>>> new_maps;
     std::vector<csdr_viewbank_item> post_items;
 };
@@ -82,14 +65,7 @@ extern "C" int csdr_viewbank_create(csdr_ctx *ctx, csdr_viewbank **out) {
     DeviceScope dev__(ctx);
     if (!ctx || !out) return fail(CSDR_EINVAL, "null argument");
     std::unique_ptr<csdr_viewbank> vb(new csdr_viewbank());
-    vb->ctx = ctx;
-    CSDR_HIP_TRY(hipStreamCreateWithFlags(&vb->st, hipStreamNonBlocking));
-    CSDR_HIP_TRY(hipEventCreateWithFlags(&vb->ev_in, hipEventDisableTiming));
-    CSDR_HIP_TRY(hipEventCreateWithFlags(&vb->ev_out, hipEventDisableTiming));
-    if (int rc = vb->plan.create()) return rc;
-    vb->trk0.ceil_ma = vb->trk0.ceil_maa = 100.0;       // ctor :32
-    vb->trk0.floor_ma = vb->trk0.floor_maa = 0.0;       // ctor :33
-    vb->trk0.ceil_peak = vb->trk0.floor_peak = 0.0;
+    if (int rc = vb->create_base(ctx)) return rc;
     *out = vb.release();
     return CSDR_OK;
 }
@@ -97,25 +73,15 @@ extern "C" int csdr_viewbank_create(csdr_ctx *ctx, csdr_viewbank **out) {
 extern "C" void csdr_viewbank_destroy(csdr_viewbank *vb) {
     DeviceScope dev__(vb ? vb->ctx : nullptr);
     if (!vb) return;
-    if (vb->st) { (void)hipStreamSynchronize(vb->st); (void)hipStreamDestroy(vb->st); }
-    if (vb->ev_in) (void)hipEventDestroy(vb->ev_in);
-    if (vb->ev_out) (void)hipEventDestroy(vb->ev_out);
-    vb->plan.destroy();
-    vb->tw4096.release(); vb->last.release(); vb->stage.release(); vb->rs.release(); vb->y.release(); vb->ma.release(); vb->maa.release();
-    vb->peak.release(); vb->trk.release(); vb->points.release(); vb->hold.release(); vb->meta.release(); vb->maps.release(); vb->maps_call.release();
-    vb->cfgs_d.release(); vb->arms_d.release();
+    vb->destroy_base();
+    vb->rs.release(); vb->y.release(); vb->maps.release(); vb->maps_call.release(); vb->cfgs_d.release(); vb->arms_d.release();
     delete vb;
 }
 
 // a slot as SpectrumVisualProcessor's constructor and setup(fftSize_in) leave it, with setPeakHold(the object's setting) and the slot's last
 // setView called once.  (The resampler's windows in HBM need no fill: the first input builds a resampler, and a new resampler starts empty.)
 static int vb_reset_slot(csdr_viewbank *vb, int slot) {
-    const size_t Fi = (size_t)vb->Fi, o = (size_t)slot * Fi;
-    CSDR_HIP_TRY(hipMemsetAsync(vb->last.p + o, 0, Fi * sizeof(float2), vb->st));
-    CSDR_HIP_TRY(hipMemsetAsync(vb->ma.p + o, 0, Fi * sizeof(double), vb->st));
-    CSDR_HIP_TRY(hipMemsetAsync(vb->maa.p + o, 0, Fi * sizeof(double), vb->st));
-    CSDR_HIP_TRY(hipMemsetAsync(vb->peak.p + o, 0, Fi * sizeof(double), vb->st));
-    CSDR_HIP_TRY(hipMemcpyAsync(vb->trk.p + slot, &vb->trk0, sizeof(SpecBankTrk), hipMemcpyHostToDevice, vb->st));
+    if (int rc = vb->reset_frames(slot)) return rc;
     VbSlot &s = vb->slots[(size_t)slot];
     VbSlot fresh;
     fresh.has_view = s.has_view; fresh.centre = s.centre; fresh.bandwidth = s.bandwidth;
@@ -127,45 +93,19 @@ static int vb_reset_slot(csdr_viewbank *vb, int slot) {
 extern "C" int csdr_viewbank_setup(csdr_viewbank *vb, int fft_size, int max_slots, int max_frames, int max_samples) {
     DeviceScope dev__(vb ? vb->ctx : nullptr);
     if (!vb) return fail(CSDR_EINVAL, "view bank is null");
-    if (fft_size < 8) return fail(CSDR_EINVAL, "fft_size %d: a power of two, 8 .. %d", fft_size, kFftMaxLds / 2);
-    if ((fft_size & (fft_size - 1)) != 0 || fft_size > kFftMaxLds / 2) return fail(CSDR_EUNSUPPORTED, "fft_size %d: a power of two, 8 .. %d", fft_size, kFftMaxLds / 2);
-    if (max_slots < 1 || max_slots > 4096) return fail(CSDR_EINVAL, "max_slots %d: 1 .. 4096", max_slots);
-    if (max_frames < 1) return fail(CSDR_EINVAL, "max_frames %d", max_frames);
+    if (int rc = sb_check_setup(fft_size, max_slots, max_frames)) return rc;
     if (max_samples < 1) return fail(CSDR_EINVAL, "max_samples %d", max_samples);
     CSDR_HIP_TRY(hipStreamSynchronize(vb->st));
     vb->ready = false;
-    const size_t Fi = 2 * (size_t)fft_size, S = (size_t)max_slots;        // SPECTRUM_VZM (.h:11, :145)
-    if (!vb->tw4096.p) {
-        std::vector<float2> t(kTwTab);
-        for (int i = 0; i < kTwTab; i++) { const double a = -2.0 * M_PI * i / kTwTab; t[(size_t)i] = make_float2((float)std::cos(a), (float)std::sin(a)); }
-        if (int rc = vb->tw4096.reserve(kTwTab)) return rc;
-        CSDR_HIP_TRY(hipMemcpy(vb->tw4096.p, t.data(), kTwTab * sizeof(float2), hipMemcpyHostToDevice));
-    }
-    if (int rc = vb->last.reserve(S * Fi)) return rc;
+    if (int rc = vb->reserve_frames(fft_size, max_slots, max_frames)) return rc;
+    const size_t Fi = (size_t)vb->Fi, S = (size_t)max_slots;
     if (int rc = vb->y.reserve(S * Fi)) return rc;
     if (int rc = vb->rs.reserve(S * (size_t)kVbState)) return rc;
-    if (int rc = vb->ma.reserve(S * Fi)) return rc;
-    if (int rc = vb->maa.reserve(S * Fi)) return rc;
-    if (int rc = vb->peak.reserve(S * Fi)) return rc;
-    if (int rc = vb->trk.reserve(S)) return rc;
     if (int rc = vb->maps.reserve(S * (size_t)fft_size)) return rc;
-    if (int rc = vb->points.reserve(S * (size_t)max_frames * (size_t)fft_size)) return rc;
-    if (int rc = vb->hold.reserve(S * (size_t)max_frames * (size_t)fft_size)) return rc;
-    if (int rc = vb->meta.reserve(S * (size_t)max_frames)) return rc;
-    // setup makes every slot a processor nobody has called setView on
-    vb->F = fft_size; vb->Fi = (int)Fi; vb->max_slots = max_slots; vb->max_frames = max_frames; vb->max_samples = max_samples;
-    vb->slots.assign(S, VbSlot());
-    vb->touched.clear();
-    CSDR_HIP_TRY(hipMemsetAsync(vb->last.p, 0, S * Fi * sizeof(float2), vb->st));
+    vb->max_samples = max_samples;
     CSDR_HIP_TRY(hipMemsetAsync(vb->y.p, 0, S * Fi * sizeof(float2), vb->st));
     CSDR_HIP_TRY(hipMemsetAsync(vb->rs.p, 0, S * (size_t)kVbState * sizeof(float2), vb->st));
-    CSDR_HIP_TRY(hipMemsetAsync(vb->ma.p, 0, S * Fi * sizeof(double), vb->st));
-    CSDR_HIP_TRY(hipMemsetAsync(vb->maa.p, 0, S * Fi * sizeof(double), vb->st));
-    CSDR_HIP_TRY(hipMemsetAsync(vb->peak.p, 0, S * Fi * sizeof(double), vb->st));
-    std::vector<SpecBankTrk> t0(S, vb->trk0);
-    CSDR_HIP_TRY(hipMemcpyAsync(vb->trk.p, t0.data(), S * sizeof(SpecBankTrk), hipMemcpyHostToDevice, vb->st));
-    CSDR_HIP_TRY(hipStreamSynchronize(vb->st));          // (t0 is this call's)
-    for (VbSlot &s : vb->slots) s.peak_reset = 1;
+    if (int rc = vb->fresh_slots()) return rc;            // every slot a processor nobody has called setView on (ends in a synchronise)
     vb->ready = true;
     return CSDR_OK;
 }
@@ -180,11 +120,9 @@ extern "C" int csdr_viewbank_set_scale_factor(csdr_viewbank *vb, float sf) {    
     vb->sf = sf;
     return CSDR_OK;
 }
-extern "C" int csdr_viewbank_set_peak_hold(csdr_viewbank *vb, int enabled) {       // setPeakHold :115-125, on every slot
+extern "C" int csdr_viewbank_set_peak_hold(csdr_viewbank *vb, int enabled) {
     if (!vb) return fail(CSDR_EINVAL, "view bank is null");
-    const bool again = vb->peak_hold && enabled;
-    for (VbSlot &s : vb->slots) s.peak_reset = again ? kVbPeakResetCount : 1;
-    if (!again) vb->peak_hold = enabled != 0;
+    vb->set_peak_hold(enabled);
     return CSDR_OK;
 }
 extern "C" int csdr_viewbank_get_peak_hold(const csdr_viewbank *vb) { return vb && vb->peak_hold ? 1 : 0; }
@@ -195,8 +133,7 @@ extern "C" int csdr_viewbank_set_hide_dc(csdr_viewbank *vb, int enabled) {      
 }
 
 extern "C" int csdr_viewbank_set_view(csdr_viewbank *vb, int slot, int64_t center_freq, int64_t bandwidth) {     // setView(true, ...) :64-72
-    if (!vb || !vb->ready) return fail(CSDR_ESTATE, "view bank not set up");
-    if (slot < 0 || slot >= vb->max_slots) return fail(CSDR_EINVAL, "slot %d of %d", slot, vb->max_slots);
+    if (int rc = sb_check_slot(vb, slot)) return rc;
     if (bandwidth <= 0) return fail(CSDR_EINVAL, "bandwidth %lld", (long long)bandwidth);
     VbSlot &s = vb->slots[(size_t)slot];
     s.has_view = true; s.centre = center_freq; s.bandwidth = bandwidth;
@@ -205,8 +142,7 @@ extern "C" int csdr_viewbank_set_view(csdr_viewbank *vb, int slot, int64_t cente
 
 extern "C" int csdr_viewbank_reset_slot(csdr_viewbank *vb, int slot) {
     DeviceScope dev__(vb ? vb->ctx : nullptr);
-    if (!vb || !vb->ready) return fail(CSDR_ESTATE, "view bank not set up");
-    if (slot < 0 || slot >= vb->max_slots) return fail(CSDR_EINVAL, "slot %d of %d", slot, vb->max_slots);
+    if (int rc = sb_check_slot(vb, slot)) return rc;
     return vb_reset_slot(vb, slot);
 }
 
@@ -251,44 +187,29 @@ static void vb_view_map(int F, int64_t bandwidth, int64_t resample_bw, std::vect
 static int vb_run(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_items, bool any_dev, csdr_post *post = nullptr) {
     const int Fi = vb->Fi, F = vb->F;
     // ---- plan on copies: a refused call leaves every slot as it was
-    vb->n_jobs_of.assign((size_t)vb->max_slots, 0);
+    vb->count_begin();
     size_t n_jobs = 0;
     for (int i = 0; i < n_items; ++i) {
         const csdr_viewbank_item &it = items[i];
         if (it.n == 0) continue;                          // no input at all
         if (!vb->slots[(size_t)it.slot].has_view) return fail(CSDR_ESTATE, "item %d: slot %d was never given a view", i, it.slot);
         if (it.n > vb->max_samples) return fail(CSDR_ERANGE, "item %d: %d samples exceed max_samples %d", i, it.n, vb->max_samples);
-        ++vb->n_jobs_of[(size_t)it.slot];
+        vb->count_job(it.slot);
         ++n_jobs;
     }
-    vb->run_slots.clear();
-    vb->job_at.assign((size_t)vb->max_slots, 0);
-    vb->work.resize((size_t)vb->max_slots);
-    {
-        int at = 0;
-        for (int s = 0; s < vb->max_slots; ++s)
-            if (vb->n_jobs_of[(size_t)s]) {
-                vb->run_slots.push_back(s); vb->job_at[(size_t)s] = at; at += vb->n_jobs_of[(size_t)s];
-                vb->work[(size_t)s] = vb->slots[(size_t)s];
-                vb->work[(size_t)s].frames = 0;
-                vb->work[(size_t)s].map_new = -1;
-            }
-    }
-    vb->jobs_h.resize(n_jobs);
+    vb->order_jobs(n_jobs);
     vb->job_map.assign(n_jobs, -1);
     vb->new_maps.clear();
-    vb->cursor = vb->job_at;
     size_t host_samples = 0;
     int S_max = 0;
     for (int i = 0; i < n_items; ++i) {
         const csdr_viewbank_item &it = items[i];
         if (it.n == 0) continue;
         VbSlot &s = vb->work[(size_t)it.slot];
-        const size_t ji = (size_t)vb->cursor[(size_t)it.slot]++;
+        const size_t ji = vb->next_job(it.slot);
         ViewBankJob jb{};
         jb.frame = -1;
-        jb.do_peak = vb->peak_hold && s.peak_reset == 0 ? 1 : 0;              // :247
-        if (s.peak_reset != 0 && --s.peak_reset == 0) jb.peak_reset_now = 1;  // :264-273
+        vb->job_head(jb, s);
         const long long rate = it.sample_rate, freq = it.frequency;
         if (rate < 0) return fail(CSDR_EINVAL, "item %d: sample rate %lld", i, rate);
         if (rate == 0) {                                                      // :284-287
@@ -319,7 +240,7 @@ static int vb_run(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_item
                     if (ns > 0.0 && ns < (double)(Fi / 2)) { jb.shift_mode = freq_diff > 0 ? kVbLeft : kVbRight; jb.shift_n = (int)ns; }
                 }
             }
-            s.peak_reset = kVbPeakResetCount;                                 // :335
+            s.peak_reset = kSbPeakResetCount;                                 // :335
         }
         bool new_resampler = false;
         long long bw_diff = 0;
@@ -333,7 +254,7 @@ static int vb_run(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_item
             s.buf_idx = 0; s.phase = 0;
             new_resampler = true;
             jb.rebuild = 1;
-            s.peak_reset = kVbPeakResetCount;                                 // :367
+            s.peak_reset = kSbPeakResetCount;                                 // :367
         }
         const ResampCfg &rc = vb->cfgs_h[(size_t)s.cfg];
         S_max = std::max(S_max, rc.S);
@@ -350,19 +271,8 @@ static int vb_run(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_item
         s.buf_idx = (uint32_t)(((uint64_t)s.buf_idx + desired) & (((uint64_t)1 << rc.S) - 1));
         jb.nw = nw;
         s.num_written = nw;
-        // the frame rule of :399-421 on num_written
-        if (nw >= Fi) { jb.action = kSbFull; jb.arg = 0; }
-        else if (s.last_size + nw < Fi) {
-            jb.action = kSbPrime;
-            jb.arg = std::max(Fi - s.last_size, nw);
-            s.last_size += jb.arg;
-        } else {
-            if (s.last_size > Fi) return fail(CSDR_ESTATE, "slot %d: lastDataSize %d beyond %d", it.slot, s.last_size, Fi);      // (cannot happen: priming stops at Fi)
-            jb.action = kSbSlide;
-            jb.arg = s.last_size - (Fi - nw);
-        }
+        if (int rc = vb->frame_rule(jb, s, it.slot, nw)) return rc;           // :399-421 on num_written
         if (jb.action != kSbPrime) {
-            jb.frame = s.frames++;
             if (new_resampler && s.last_view) jb.rescale = bw_diff < 0 ? kVbSqueeze : kVbStretch;      // :454
             if (s.map_bw != s.bandwidth || s.map_rbw != rbw) {
                 vb->new_maps.emplace_back(it.slot, std::vector<int2>());
@@ -381,14 +291,9 @@ static int vb_run(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_item
         if (!it.is_dev) host_samples += (size_t)jb.n;
         vb->jobs_h[ji] = jb;
     }
-    for (int s : vb->run_slots)
-        if (vb->work[(size_t)s].frames > vb->max_frames)
-            return fail(CSDR_ERANGE, "slot %d: %d frames in one call exceed max_frames %d", s, vb->work[(size_t)s].frames, vb->max_frames);
-    // ---- commit the host state; from here on the call is enqueued
-    for (int s : vb->touched) vb->slots[(size_t)s].frames = 0;
-    vb->touched = vb->run_slots;
-    for (int s : vb->run_slots) { vb->slots[(size_t)s] = vb->work[(size_t)s]; vb->slots[(size_t)s].map_new = -1; }
-    vb->sf_last = vb->sf;
+    if (int rc = vb->check_frames()) return rc;
+    vb->commit();
+    for (int s : vb->run_slots) vb->slots[(size_t)s].map_new = -1;
     if (n_jobs == 0) return CSDR_OK;
     hipStream_t st = vb->st;
     if (post) {      // the rows of the channelizer's batch are complete
@@ -432,39 +337,11 @@ static int vb_run(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_item
             vb->jobs_h[ji].map = mi < 0 ? vb->maps.p + (size_t)s * (size_t)F : vb->maps_call.p + (size_t)mi * (size_t)F;
         }
     }
-    if (host_samples) {
-        if (host_samples > vb->stage.cap) CSDR_HIP_TRY(hipStreamSynchronize(st));        // (a kernel may still read the buffer being replaced)
-        if (int rc = vb->stage.reserve(host_samples)) return rc;
-        size_t at = 0;
-        vb->cursor = vb->job_at;
-        for (int i = 0; i < n_items; ++i) {                // host inputs, staged in item order: the samples the input consumes
-            const csdr_viewbank_item &it = items[i];
-            if (it.n == 0) continue;
-            ViewBankJob &jb = vb->jobs_h[(size_t)vb->cursor[(size_t)it.slot]++];
-            if (it.is_dev || jb.action == kVbNone) continue;
-            float2 *dst = vb->stage.p + at;
-            CSDR_HIP_TRY(hipMemcpyAsync(dst, it.iq, (size_t)jb.n * sizeof(float2), hipMemcpyHostToDevice, st));
-            jb.src = dst;
-            at += (size_t)jb.n;
-        }
-    }
-    const size_t n_runs = vb->run_slots.size();
-    const size_t bytes = n_runs * sizeof(SpecBankRun) + n_jobs * sizeof(ViewBankJob);
-    if (int rc = vb->plan.begin(st, bytes)) return rc;               // the one host wait of a call
-    SpecBankRun *runs_h = reinterpret_cast<SpecBankRun *>(vb->plan.host());
-    for (size_t r = 0; r < n_runs; ++r) {
-        const int s = vb->run_slots[r];
-        runs_h[r] = SpecBankRun{s, vb->job_at[(size_t)s], vb->n_jobs_of[(size_t)s], 0};
-    }
-    memcpy(vb->plan.host() + n_runs * sizeof(SpecBankRun), vb->jobs_h.data(), n_jobs * sizeof(ViewBankJob));
-    if (int rc = vb->plan.uploaded(st, bytes)) return rc;
+    if (int rc = vb->stage_inputs(items, n_items, host_samples)) return rc;
     ViewBankArgs a{};
-    a.runs = reinterpret_cast<const SpecBankRun *>(vb->plan.device());
-    a.jobs = reinterpret_cast<const ViewBankJob *>(vb->plan.device() + n_runs * sizeof(SpecBankRun));
-    a.tw4096 = vb->tw4096.p; a.sintab = vb->ctx->sintab.p; a.cfgs = vb->cfgs_d.p; a.arms = vb->arms_d.p;
-    a.last = vb->last.p; a.ma = vb->ma.p; a.maa = vb->maa.p; a.peak = vb->peak.p; a.trk = vb->trk.p; a.rs = vb->rs.p; a.y = vb->y.p;
-    a.points = vb->points.p; a.hold = vb->hold.p; a.meta = vb->meta.p;
-    a.Fi = Fi; a.max_frames = vb->max_frames; a.rate = (double)vb->avg_rate; a.sf = vb->sf;
+    if (int rc = vb->upload_plan(&a.runs, &a.jobs)) return rc;
+    vb->fill_args(a);
+    a.sintab = vb->ctx->sintab.p; a.cfgs = vb->cfgs_d.p; a.arms = vb->arms_d.p; a.rs = vb->rs.p; a.y = vb->y.p;
     const size_t lds = viewbank_lds_bytes(Fi, S_max);
     if (lds > 64 * 1024 && lds > vb->lds_attr) {
         CSDR_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(viewbank_process), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -472,7 +349,7 @@ static int vb_run(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_item
     }
     {
         ProfScope ps__(vb->ctx, KID_VIEWBANK, st);
-        hipLaunchKernelGGL(viewbank_process, dim3((unsigned)n_runs), dim3(kFftThreads), lds, st, a);
+        hipLaunchKernelGGL(viewbank_process, dim3((unsigned)vb->run_slots.size()), dim3(kFftThreads), lds, st, a);
     }
     CSDR_HIP_TRY(hipGetLastError());
     {   // each slot's latest map of this call becomes the slot's, behind the kernel that may still read the previous one
@@ -495,24 +372,15 @@ static int vb_run(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_item
 
 extern "C" int csdr_viewbank_process(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_items) {
     DeviceScope dev__(vb ? vb->ctx : nullptr);
-    if (!vb || !vb->ready) return fail(CSDR_ESTATE, "view bank not set up");
-    if (n_items < 0 || (n_items > 0 && !items)) return fail(CSDR_EINVAL, "bad items");
+    if (int rc = sb_check_ready(vb)) return rc;
     bool any_dev = false;
-    for (int i = 0; i < n_items; ++i) {
-        const csdr_viewbank_item &it = items[i];
-        if (it.slot < 0 || it.slot >= vb->max_slots) return fail(CSDR_EINVAL, "item %d: slot %d of %d", i, it.slot, vb->max_slots);
-        if (it.n < 0 || (it.n > 0 && !it.iq)) return fail(CSDR_EINVAL, "item %d: %d samples at %p", i, it.n, (const void *)it.iq);
-        if (it.n > 0 && it.is_dev) {
-            if ((uintptr_t)it.iq & 7) return fail(CSDR_EINVAL, "item %d: device samples must be 8-byte aligned", i);
-            any_dev = true;
-        }
-    }
+    if (int rc = sb_check_items(items, n_items, vb->max_slots, &any_dev)) return rc;
     return vb_run(vb, items, n_items, any_dev);
 }
 
 extern "C" int csdr_viewbank_process_post(csdr_viewbank *vb, csdr_post *post, const int *slots, const int *channels, int n) {
     DeviceScope dev__(vb ? vb->ctx : nullptr);
-    if (!vb || !vb->ready) return fail(CSDR_ESTATE, "view bank not set up");
+    if (int rc = sb_check_ready(vb)) return rc;
     if (!post || n < 0 || (n > 0 && (!slots || !channels))) return fail(CSDR_EINVAL, "bad argument");
     if (post->ctx != vb->ctx) return fail(CSDR_EINVAL, "the channelizer belongs to another context");
     if (!post->row_order.empty()) return fail(CSDR_EINVAL, "the post has packed rows (a time-slab producer): views read the owner's post");
@@ -536,66 +404,25 @@ extern "C" int csdr_viewbank_process_post(csdr_viewbank *vb, csdr_post *post, co
     return vb_run(vb, vb->post_items.data(), (int)vb->post_items.size(), false, post);
 }
 
-extern "C" int csdr_viewbank_frames(const csdr_viewbank *vb, int slot) {
-    return vb && vb->ready && slot >= 0 && slot < vb->max_slots ? vb->slots[(size_t)slot].frames : 0;
-}
-
-static int vb_check_frame(const csdr_viewbank *vb, int slot, int frame) {
-    if (!vb || !vb->ready) return fail(CSDR_ESTATE, "view bank not set up");
-    if (slot < 0 || slot >= vb->max_slots) return fail(CSDR_EINVAL, "slot %d of %d", slot, vb->max_slots);
-    if (frame < 0 || frame >= vb->slots[(size_t)slot].frames) return fail(CSDR_EINVAL, "frame %d of %d", frame, vb->slots[(size_t)slot].frames);
-    return CSDR_OK;
-}
-
-// SpectrumVisualData of a frame: the device keeps only the y of every point; the x of point i is (float)i / (float)fftSize (:563)
-static int vb_fetch(csdr_viewbank *vb, const float *src, size_t fo, float *host, SpecBankFrame *m) {
-    const int F = vb->F;
-    CSDR_HIP_TRY(hipMemcpyAsync(host + F, src + fo * (size_t)F, (size_t)F * sizeof(float), hipMemcpyDeviceToHost, vb->st));
-    CSDR_HIP_TRY(hipMemcpyAsync(m, vb->meta.p + fo, sizeof(SpecBankFrame), hipMemcpyDeviceToHost, vb->st));
-    CSDR_HIP_TRY(hipStreamSynchronize(vb->st));
-    for (int i = 0; i < F; ++i) { const float y = host[F + i]; host[2 * i] = (float)i / (float)F; host[2 * i + 1] = y; }
-    return CSDR_OK;
-}
+extern "C" int csdr_viewbank_frames(const csdr_viewbank *vb, int slot) { return sb_frames(vb, slot); }
 
 extern "C" int csdr_viewbank_fetch(csdr_viewbank *vb, int slot, int frame, float *points_host, int cap_floats, double *fft_ceiling, double *fft_floor) {
     DeviceScope dev__(vb ? vb->ctx : nullptr);
-    if (int rc = vb_check_frame(vb, slot, frame)) return rc;
-    if (!points_host) return fail(CSDR_EINVAL, "null argument");
-    if (cap_floats < 2 * vb->F) return fail(CSDR_ERANGE, "need room for %d floats", 2 * vb->F);
-    SpecBankFrame m{};
-    const size_t fo = (size_t)slot * (size_t)vb->max_frames + (size_t)frame;
-    if (int rc = vb_fetch(vb, vb->points.p, fo, points_host, &m)) return rc;
-    if (fft_ceiling) *fft_ceiling = m.point_ceil / vb->sf_last;          // :626
-    if (fft_floor) *fft_floor = m.point_floor;                           // :627
-    return CSDR_OK;
+    return sb_fetch(vb, slot, frame, points_host, cap_floats, fft_ceiling, fft_floor);
 }
 
 extern "C" int csdr_viewbank_fetch_hold(csdr_viewbank *vb, int slot, int frame, float *hold_host, int cap_floats, int *n_floats) {
     DeviceScope dev__(vb ? vb->ctx : nullptr);
-    if (n_floats) *n_floats = 0;
-    if (int rc = vb_check_frame(vb, slot, frame)) return rc;
-    if (!hold_host || !n_floats) return fail(CSDR_EINVAL, "null argument");
-    if (cap_floats < 2 * vb->F) return fail(CSDR_ERANGE, "need room for %d floats", 2 * vb->F);
-    SpecBankFrame m{};
-    const size_t fo = (size_t)slot * (size_t)vb->max_frames + (size_t)frame;
-    if (int rc = vb_fetch(vb, vb->hold.p, fo, hold_host, &m)) return rc;
-    *n_floats = m.hold ? 2 * vb->F : 0;
-    return CSDR_OK;
+    return sb_fetch_hold(vb, slot, frame, hold_host, cap_floats, n_floats);
 }
 
 extern "C" int csdr_viewbank_device_points(csdr_viewbank *vb, int slot, const float **dev, int *frames) {
     DeviceScope dev__(vb ? vb->ctx : nullptr);
-    if (!vb || !vb->ready) return fail(CSDR_ESTATE, "view bank not set up");
-    if (!dev || slot < 0 || slot >= vb->max_slots) return fail(CSDR_EINVAL, "bad argument");
-    CSDR_HIP_TRY(hipEventRecord(vb->ev_out, vb->st));     // whatever the caller enqueues on the boundary stream next reads the finished points
-    CSDR_HIP_TRY(hipStreamWaitEvent(vb->ctx->stream, vb->ev_out, 0));
-    *dev = vb->points.p + (size_t)slot * (size_t)vb->max_frames * (size_t)vb->F;
-    if (frames) *frames = vb->slots[(size_t)slot].frames;
-    return CSDR_OK;
+    return sb_device_points(vb, slot, dev, frames);
 }
 
 extern "C" int csdr_viewbank_slot_info(const csdr_viewbank *vb, int slot, csdr_viewbank_slot_state *out) {
-    if (!vb || !vb->ready) return fail(CSDR_ESTATE, "view bank not set up");
+    if (int rc = sb_check_ready(vb)) return rc;
     if (!out || slot < 0 || slot >= vb->max_slots) return fail(CSDR_EINVAL, "bad argument");
     const VbSlot &s = vb->slots[(size_t)slot];
     out->resample_bw = s.resample_bw; out->shift_frequency = s.shift_frequency;
@@ -605,7 +432,7 @@ extern "C" int csdr_viewbank_slot_info(const csdr_viewbank *vb, int slot, csdr_v
 
 extern "C" int csdr_viewbank_fetch_last(csdr_viewbank *vb, int slot, float *out, int cap_floats) {
     DeviceScope dev__(vb ? vb->ctx : nullptr);
-    if (!vb || !vb->ready) return fail(CSDR_ESTATE, "view bank not set up");
+    if (int rc = sb_check_ready(vb)) return rc;
     if (!out || slot < 0 || slot >= vb->max_slots) return fail(CSDR_EINVAL, "bad argument");
     if (cap_floats < 2 * vb->Fi) return fail(CSDR_ERANGE, "need room for %d floats", 2 * vb->Fi);
     CSDR_HIP_TRY(hipMemcpyAsync(out, vb->last.p + (size_t)slot * (size_t)vb->Fi, (size_t)vb->Fi * sizeof(float2), hipMemcpyDeviceToHost, vb->st));

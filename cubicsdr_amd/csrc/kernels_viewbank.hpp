@@ -19,9 +19,9 @@
 //      carried as state: per stage the last kFeTail even / odd samples, the last kFeZTail chain outputs, and the mixed samples that do not yet fill a
 //      group of 2^S (msresamp's buffer_index).  Every output is one dot product over positions of the slot's stream: bit for bit the same however
 //      the inputs are cut into calls.  The first Fi outputs go to the slot's `y` row in HBM.
-//   B  the statements of specbank_process on that row, with the averagers' moves staged through LDS (every kept value is read before any is
-//      written) and the display walking the view map.  These per-frame statements are a SECOND statement of the spectrum bank's (the
-//      pair loop, the reductions and the trackers are the same lines; the point loop differs).
+//   B  the per-frame functions of kernels_specbank.hpp (sb_prime, sb_transform, sb_average, sb_scale, sb_point, sb_store_meta: ONE statement for
+//      both banks) on that row, with the averagers' moves staged through LDS in front of them (every kept value is read before any is written).
+//      What is stated here is what differs: the point loop walks the view map and gathers through the hideDC span.
 // The kernel is latency-bound by design, as specbank_process is.  All LDS is dynamic (`smem`): the larger of the two phases' needs.
 #pragma once
 #include "common.hpp"
@@ -219,11 +219,7 @@ CSDR_KERNEL_VB __launch_bounds__(kFftThreads) void viewbank_process(ViewBankArgs
     SpecBankTrk t = a.trk[run.slot];                                       // every thread carries the trackers
     for (int jn = 0; jn < run.n_jobs; ++jn) {
         const ViewBankJob jb = a.jobs[run.job0 + jn];
-        if (jb.peak_reset_now) {                                           // :266-272, with the trackers as they stand in front of this input
-            for (int i = tid; i < Fi; i += kFftThreads) peak[i] = t.floor_maa;
-            t.ceil_peak = t.floor_maa;
-            t.floor_peak = t.ceil_maa;
-        }
+        if (jb.peak_reset_now) sb_peak_reset(peak, t, Fi);
         if (jb.action == kVbNone) { __syncthreads(); continue; }           // :284-287
         if (jb.shift_mode) {                                               // :316-331 (the peak array stays)
             vb_move(ma, jb.shift_mode, jb.shift_n, Fi, s_stage);
@@ -231,55 +227,14 @@ CSDR_KERNEL_VB __launch_bounds__(kFftThreads) void viewbank_process(ViewBankArgs
         }
         vb_resample(jb, a.cfgs[jb.cfg], a.arms + (size_t)jb.cfg * kArms * kArmTaps, a.sintab, pend, tails, ztail, y, Fi, smem);
         const int nw = min(jb.nw, Fi);                                     // fftInData holds Fi samples (:388-396)
-        if (jb.action == kSbPrime) {                                       // :407-413: the data followed by zeros
-            for (int i = tid; i < jb.arg; i += kFftThreads) last[i] = i < nw ? y[i] : make_float2(0.f, 0.f);
-            __syncthreads();
-            continue;
-        }
+        if (jb.action == kSbPrime) { sb_prime(last, y, nw, jb.arg); continue; }
         if (jb.rescale) {                                                  // :454-492
             vb_move(ma, jb.rescale, 0, Fi, s_stage);
             vb_move(maa, jb.rescale, 0, Fi, s_stage);
         }
-        const int keep = Fi - nw;                                          // 0 for FULL
-        for (int i = tid; i < Fi; i += kFftThreads) sa[i] = i < keep ? last[jb.arg + i] : y[i - keep];
-        __syncthreads();
-        for (int i = tid; i < Fi; i += kFftThreads) last[i] = sa[i];
-        const float2 *X = lds_fft(sa, sb, Fi, a.tw4096);
-        double mx = 0.0, mn = 1.0;
-        for (int x = tid; x < F; x += kFftThreads) {                       // a thread takes two adjacent bins
-            const int k = (2 * x + F) & (Fi - 1);
-            const float2 va = X[k], vb = X[k + 1];
-            const float ra = sqrtf(rounded(va.x * va.x) + rounded(va.y * va.y));
-            const float rb = sqrtf(rounded(vb.x * vb.x) + rounded(vb.y * vb.y));
-            AvgState s;
-            s.ma_a = ma[2 * x]; s.ma_b = ma[2 * x + 1]; s.maa_a = maa[2 * x]; s.maa_b = maa[2 * x + 1];
-            avg_step(s, (double)ra, (double)rb, a.rate);
-            ma[2 * x] = s.ma_a; ma[2 * x + 1] = s.ma_b; maa[2 * x] = s.maa_a; maa[2 * x + 1] = s.maa_b;
-            mx = fmax(mx, fmax(s.maa_a, s.maa_b)); mn = fmin(mn, fmin(s.maa_a, s.maa_b));
-            if (jb.do_peak) {
-                if (s.maa_a > peak[2 * x]) peak[2 * x] = s.maa_a;
-                if (s.maa_b > peak[2 * x + 1]) peak[2 * x + 1] = s.maa_b;
-            }
-        }
-        for (int o = 32; o > 0; o >>= 1) { mx = fmax(mx, __shfl_down(mx, o, 64)); mn = fmin(mn, __shfl_down(mn, o, 64)); }
-        if ((tid & 63) == 0) { s_red[tid >> 6] = mx; s_red[4 + (tid >> 6)] = mn; }
-        __syncthreads();                                                    // (also: every thread's maa[] / peak[] store is visible to the workgroup)
-        const float fft_ceil = (float)fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
-        const float fft_floor = (float)fmin(fmin(s_red[4], s_red[5]), fmin(s_red[6], s_red[7]));
-        if (t.ceil_ma != t.ceil_ma) t.ceil_ma = fft_ceil;                   // :513-521
-        t.ceil_ma = t.ceil_ma + ((double)fft_ceil - t.ceil_ma) * 0.05;
-        if (t.ceil_maa != t.ceil_maa) t.ceil_maa = fft_ceil;
-        t.ceil_maa = t.ceil_maa + (t.ceil_ma - t.ceil_maa) * 0.05;
-        if (t.floor_ma != t.floor_ma) t.floor_ma = fft_floor;
-        t.floor_ma = t.floor_ma + ((double)fft_floor - t.floor_ma) * 0.05;
-        if (t.floor_maa != t.floor_maa) t.floor_maa = fft_floor;
-        t.floor_maa = t.floor_maa + (t.floor_ma - t.floor_maa) * 0.05;
-        if (jb.do_peak) {                                                   // :523-530
-            if (t.ceil_maa > t.ceil_peak) t.ceil_peak = t.ceil_maa;
-            if (t.floor_maa < t.floor_peak) t.floor_peak = t.floor_maa;
-        }
-        const double pc = jb.do_peak ? t.ceil_peak : t.ceil_maa, pf = jb.do_peak ? t.floor_peak : t.floor_maa;    // :539-540
-        const double den = log10((pc + 0.25) - (pf - 0.75));
+        const float2 *X = sb_transform(last, y, nw, jb.arg, Fi, sa, sb, a.tw4096);
+        sb_average(X, ma, maa, peak, s_red, t, Fi, a.rate, jb.do_peak);
+        const SpecBankScale sc = sb_scale(t, jb.do_peak);
         const size_t fo = (size_t)run.slot * a.max_frames + (size_t)jb.frame;
         float *out = a.points + fo * F, *hold = a.hold + fo * F;
         HideDcSpan dc;
@@ -293,14 +248,10 @@ CSDR_KERNEL_VB __launch_bounds__(kFftThreads) void viewbank_process(ViewBankArgs
                 acc += in ? maa[idx] : t.floor_maa;
                 if (jb.do_peak) pacc += in ? peak[idx] : t.floor_maa;
             }
-            out[x] = (float)((log10((acc / (double)m.y) + 0.25 - (pf - 0.75)) / den) * (double)a.sf);
-            if (jb.do_peak) hold[x] = (float)((log10((pacc / (double)m.y) + 0.25 - (pf - 0.75)) / den) * (double)a.sf);
+            out[x] = sb_point(acc, (double)m.y, sc, a.sf);
+            if (jb.do_peak) hold[x] = sb_point(pacc, (double)m.y, sc, a.sf);
         }
-        if (tid == 0) {
-            SpecBankFrame m;
-            m.point_ceil = pc; m.point_floor = pf; m.hold = jb.do_peak; m.pad = 0;
-            a.meta[fo] = m;
-        }
+        sb_store_meta(a.meta + fo, sc, jb.do_peak);
         __syncthreads();                                                    // the LDS arrays, `last` and the averagers are reused by the next job
     }
     if (tid == 0) a.trk[run.slot] = t;
