@@ -46,9 +46,8 @@ extern "C" int csdr_bank_create(csdr_ctx *ctx, int max_demods, int max_blocks, c
     b->table_bytes = (b->off_plans + (size_t)max_demods * (max_blocks + 1) * sizeof(BlockPlan) + 255) & ~(size_t)255;
     if (int rc = b->tables.reserve(2 * b->table_bytes)) return rc;
     for (int k = 0; k < 2; ++k) {
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_fe_done[k], hipEventDisableTiming));
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_audio_done[k], hipEventDisableTiming));
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_tables_read[k], hipEventDisableTiming));
+        if (int rc = order_event(&b->ev_fe_done[k])) return rc;
+        if (int rc = order_event(&b->ev_audio_done[k])) return rc;
     }
     if (int rc = b->mconsts.reserve(1)) return rc;
     for (int r = 0; r < kStageRing; ++r) {
@@ -82,18 +81,11 @@ extern "C" void csdr_bank_destroy(csdr_bank *b) {
     for (int k = 0; k < 2; ++k) {
         if (b->ev_fe_done[k]) (void)hipEventDestroy(b->ev_fe_done[k]);
         if (b->ev_audio_done[k]) (void)hipEventDestroy(b->ev_audio_done[k]);
-        if (b->ev_tables_read[k]) (void)hipEventDestroy(b->ev_tables_read[k]);
-        if (b->iq_read_pending[k]) (void)hipEventSynchronize(b->ev_iq_read[k]);      // (a reader on a stream that is not the context's)
-        if (b->ev_iq_read[k]) (void)hipEventDestroy(b->ev_iq_read[k]);
+        b->tables_read[k].destroy();
+        b->iq[k].destroy();                  // (host-waits for a reader on a stream that is not the context's)
+        b->plan[k].destroy();
     }
-    if (b->ev_iq_ready) (void)hipEventDestroy(b->ev_iq_ready);
-    if (b->audio_read_pending) (void)hipEventSynchronize(b->ev_audio_read);
-    if (b->ev_audio_read) (void)hipEventDestroy(b->ev_audio_read);
-    if (b->ev_audio_ready) (void)hipEventDestroy(b->ev_audio_ready);
-    for (int k = 0; k < 2; ++k) {
-        if (b->plan_read_pending[k]) (void)hipEventSynchronize(b->ev_plan_read[k]);
-        if (b->ev_plan_read[k]) (void)hipEventDestroy(b->ev_plan_read[k]);
-    }
+    b->audio.destroy();
     for (auto &s : b->slots) if (s.slab) (void)hipFree(s.slab);
     b->cfgs.release(); b->tables.release(); b->arms.release(); b->mconsts.release();
     for (int r = 0; r < kStageRing; ++r) {
@@ -522,10 +514,7 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
     // BEFORE the lane waits for the channelizer (on separate streams the fetch runs beside it), the front-end kernels behind that wait
     const int pk = post->cur;
     if (b->audio_pending[bpar]) if (int rc = c->wait(b->ev_audio_done[bpar], LANE_AUDIO, LANE_FE)) return rc;
-    if (b->iq_read_pending[bpar]) {          // a device-side reader of this parity's resampled IQ (bank_iq_release): the front-end rewrites it behind that reader
-        CSDR_HIP_TRY(hipStreamWaitEvent(st, b->ev_iq_read[bpar], 0));
-        b->iq_read_pending[bpar] = false;
-    }
+    if (int rc = b->iq[bpar].wait(st)) return rc;      // device-side readers of this parity's resampled IQ (bank_iq_release): the front-end rewrites it behind them
     // Where the channelizer has a stream of its own, the fetch rides on THAT stream, behind the channelizer of this batch: a one-block call is bound by
     // the chain of the demodulators' stream (tables 4 + front-end 19 + modem / audio 22 us and three gaps), the channelizer's stream has
     // half of that; the front-end's wait for the channelizer becomes its wait for the fetch (one event either way).
@@ -535,11 +524,8 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
         const int n16 = (int)((bytes + 15) / 16);                   // (the slot and the device table are whole multiples of 256 bytes)
         // (the device copy of this parity was last read by the audio kernels two batches ago: the demodulators' stream orders that by itself,
         //  the channelizer's stream waits for the event recorded behind them)
-        if (fetch_on_post && b->tables_read_pending[bpar]) CSDR_HIP_TRY(hipStreamWaitEvent(c->lanes[LANE_POST], b->ev_tables_read[bpar], 0));
-        if (b->plan_read_pending[bpar]) {    // a device-side reader of this copy's block plan (bank_plan_release): the fetch rewrites it behind that reader
-            CSDR_HIP_TRY(hipStreamWaitEvent(fetch_on_post ? c->lanes[LANE_POST] : st, b->ev_plan_read[bpar], 0));
-            b->plan_read_pending[bpar] = false;
-        }
+        if (fetch_on_post) if (int rc = b->tables_read[bpar].wait(c->lanes[LANE_POST])) return rc;
+        if (int rc = b->plan[bpar].wait(fetch_on_post ? c->lanes[LANE_POST] : st)) return rc;      // device-side readers of this copy's block plan (bank_plan_release): the fetch rewrites it behind them
         CSDR_LAUNCH(c, fetch_on_post ? LANE_POST : LANE_FE, KID_TABLES, bank_tables_fetch, dim3(std::max(1, std::min(64, (n16 + 255) / 256))), dim3(256), 0,
                     reinterpret_cast<const float4 *>(table_h), reinterpret_cast<float4 *>(table_d), n16);
         CSDR_HIP_TRY(hipGetLastError());
@@ -678,10 +664,7 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
     if (int rc = c->signal(b->ev_fe_done[bpar], LANE_FE, LANE_AUDIO)) return rc;
     // lane AUDIO: modem + audio kernels of this batch
     if (int rc = c->wait(b->ev_fe_done[bpar], LANE_FE, LANE_AUDIO)) return rc;
-    if (b->audio_read_pending) {             // a device-side reader of the audio / scope taps (bank_audio_release): the kernels below rewrite them behind that reader
-        CSDR_HIP_TRY(hipStreamWaitEvent(st_a, b->ev_audio_read, 0));
-        b->audio_read_pending = false;
-    }
+    if (int rc = b->audio.wait(st_a)) return rc;       // device-side readers of the audio / scope taps (bank_audio_release): the kernels below rewrite them behind them
     if (fused1) {
         if (n_audio_run > 0)
             CSDR_LAUNCH(c, LANE_AUDIO, KID_AUDIO, demod_modem_audio1, dim3(n_audio_run), dim3(audio_threads), std::max(modem_lds, audio_lds), b->cfgs.p, dyns_d, lists_d, plans_d,
@@ -713,58 +696,32 @@ extern "C" int csdr_bank_execute(csdr_bank *b, const csdr_post *post) {
     CSDR_HIP_TRY(hipGetLastError());
     if (int rc = c->signal(b->ev_audio_done[bpar], LANE_AUDIO, LANE_FE)) return rc;
     b->audio_pending[bpar] = true;
-    if (fetch_on_post) { CSDR_HIP_TRY(hipEventRecord(b->ev_tables_read[bpar], st_a)); b->tables_read_pending[bpar] = true; }      // the last reader of this parity's device tables
+    if (fetch_on_post) if (int rc = b->tables_read[bpar].release(st_a)) return rc;       // the last reader of this parity's device tables
     (void)st_a;
     b->seq++;
     return CSDR_OK;
 }
 
 // ---- the resampled IQ of the last execute for a reader that stays on the device (csdr_objects.hpp) ----
+// (by parity of the batch that is read: a slot's buffer of that batch is rewritten two of the slot's batches later at the earliest)
 int bank_iq_acquire(csdr_bank *b, hipStream_t reader) {
     if (!b || b->last_nb == 0) return fail(CSDR_ESTATE, "no csdr_bank_execute yet");
-    if (!b->ev_iq_ready) {
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_iq_ready, hipEventDisableTiming));
-        for (int k = 0; k < 2; ++k) CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_iq_read[k], hipEventDisableTiming));
-    }
-    CSDR_HIP_TRY(hipEventRecord(b->ev_iq_ready, b->ctx->lanes[LANE_FE]));
-    CSDR_HIP_TRY(hipStreamWaitEvent(reader, b->ev_iq_ready, 0));
-    return CSDR_OK;
+    return b->iq[(b->seq - 1) & 1].acquire(b->ctx->lanes[LANE_FE], reader);
 }
 int bank_iq_release(csdr_bank *b, hipStream_t reader) {
     if (b->seq == 0) return CSDR_OK;         // no batch has run a slot: nothing was read
-    const int par = (int)((b->seq - 1) & 1); // the batch that was read; a slot's buffer of that batch is rewritten two of the slot's batches later at the earliest
-    CSDR_HIP_TRY(hipEventRecord(b->ev_iq_read[par], reader));
-    b->iq_read_pending[par] = true;
-    return CSDR_OK;
+    return b->iq[(b->seq - 1) & 1].release(reader);
 }
 
 // ---- the audio and scope taps of the last execute for a reader that stays on the device (csdr_objects.hpp) ----
 int bank_audio_acquire(csdr_bank *b, hipStream_t reader) {
     if (!b || b->last_nb == 0) return fail(CSDR_ESTATE, "no csdr_bank_execute yet");
-    if (!b->ev_audio_ready) {
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_audio_ready, hipEventDisableTiming));
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_audio_read, hipEventDisableTiming));
-    }
-    CSDR_HIP_TRY(hipEventRecord(b->ev_audio_ready, b->ctx->lanes[LANE_AUDIO]));
-    CSDR_HIP_TRY(hipStreamWaitEvent(reader, b->ev_audio_ready, 0));
-    return CSDR_OK;
+    return b->audio.acquire(b->ctx->lanes[LANE_AUDIO], reader);
 }
-int bank_audio_release(csdr_bank *b, hipStream_t reader) {
-    // ONE event stands for every reader of a batch: a second reader (a scope bank and a squelch bank behind the same execute) first waits for the
-    // first one's mark, so that the mark it leaves covers both
-    if (b->audio_read_pending) CSDR_HIP_TRY(hipStreamWaitEvent(reader, b->ev_audio_read, 0));
-    CSDR_HIP_TRY(hipEventRecord(b->ev_audio_read, reader));
-    b->audio_read_pending = true;
-    return CSDR_OK;
-}
+int bank_audio_release(csdr_bank *b, hipStream_t reader) { return b->audio.release(reader); }      // (a scope bank and a squelch bank behind the same execute: two readers)
 int bank_plan_release(csdr_bank *b, hipStream_t reader) {
     if (b->seq == 0) return CSDR_OK;         // no batch has run a slot: nothing was read
-    const int par = (int)((b->seq - 1) & 1);
-    if (!b->ev_plan_read[par]) CSDR_HIP_TRY(hipEventCreateWithFlags(&b->ev_plan_read[par], hipEventDisableTiming));
-    if (b->plan_read_pending[par]) CSDR_HIP_TRY(hipStreamWaitEvent(reader, b->ev_plan_read[par], 0));
-    CSDR_HIP_TRY(hipEventRecord(b->ev_plan_read[par], reader));
-    b->plan_read_pending[par] = true;
-    return CSDR_OK;
+    return b->plan[(b->seq - 1) & 1].release(reader);
 }
 
 extern "C" int csdr_bank_fetch_results(csdr_bank *b, int slot, csdr_block_result *out, int cap_blocks, int *n_blocks) {

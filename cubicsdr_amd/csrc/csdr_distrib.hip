@@ -14,9 +14,7 @@
 
 using namespace csdr;
 
-struct csdr_distrib {
-    csdr_ctx *ctx = nullptr;
-    hipStream_t st = nullptr;
+struct csdr_distrib : SideStream {               // (ev_in: the producer of a device block -- the boundary stream, then the spectrum's FFT lane)
     int max_lines = 0;
     int fft_size = 2048, lps = 30;                     // setFFTSize / setLinesPerSecond: DEFAULT_FFT_SIZE, DEFAULT_WATERFALL_LPS (ctor :11); read at the next push
     // FFTDataDistributor's state
@@ -33,10 +31,9 @@ struct csdr_distrib {
     DevBuf<int> starts[2];
     PinBuf<int> starts_h[2];
     int cur = 1;                                       // batch of the last push
-    hipEvent_t ev_in = nullptr, ev_lane = nullptr;     // boundary stream -> st, spectrum FFT lane -> st (the producer of a device block)
     hipEvent_t ev_gather[2] = {nullptr, nullptr};      // behind the gather that filled batch k
-    hipEvent_t ev_read[2] = {nullptr, nullptr};        // behind the spectrum's reads of batch k (csdr_spec_process_distrib)
-    bool gathered[2] = {false, false}, read_pending[2] = {false, false};
+    bool gathered[2] = {false, false};
+    ReadGate read[2];                                  // the spectrum's reads of batch k (csdr_spec_process_distrib); the readers wait for ev_gather
     DevBuf<float2> stage;                              // a host block on its way
 };
 
@@ -45,13 +42,10 @@ extern "C" int csdr_distrib_create(csdr_ctx *ctx, int max_lines, csdr_distrib **
     if (!ctx || !out) return fail(CSDR_EINVAL, "null argument");
     if (max_lines < 1 || max_lines > (1 << 24)) return fail(CSDR_EINVAL, "max_lines %d: 1 .. 2^24", max_lines);
     std::unique_ptr<csdr_distrib, void (*)(csdr_distrib *)> d(new csdr_distrib(), csdr_distrib_destroy);
-    d->ctx = ctx; d->max_lines = max_lines;
-    CSDR_HIP_TRY(hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking));
-    CSDR_HIP_TRY(hipEventCreateWithFlags(&d->ev_in, hipEventDisableTiming));
-    CSDR_HIP_TRY(hipEventCreateWithFlags(&d->ev_lane, hipEventDisableTiming));
+    d->max_lines = max_lines;
+    if (int rc = d->create(ctx)) return rc;
     for (int k = 0; k < 2; ++k) {
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&d->ev_gather[k], hipEventDisableTiming));
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&d->ev_read[k], hipEventDisableTiming));
+        if (int rc = order_event(&d->ev_gather[k])) return rc;
         if (int rc = d->starts[k].reserve((size_t)max_lines)) return rc;
         if (int rc = d->starts_h[k].reserve((size_t)max_lines)) return rc;
     }
@@ -62,13 +56,10 @@ extern "C" int csdr_distrib_create(csdr_ctx *ctx, int max_lines, csdr_distrib **
 extern "C" void csdr_distrib_destroy(csdr_distrib *d) {
     DeviceScope dev__(d ? d->ctx : nullptr);
     if (!d) return;
-    for (int k = 0; k < 2; ++k) if (d->read_pending[k]) (void)hipEventSynchronize(d->ev_read[k]);      // (a spectrum may still read the batch)
-    if (d->st) { (void)hipStreamSynchronize(d->st); (void)hipStreamDestroy(d->st); }
-    if (d->ev_in) (void)hipEventDestroy(d->ev_in);
-    if (d->ev_lane) (void)hipEventDestroy(d->ev_lane);
+    for (int k = 0; k < 2; ++k) d->read[k].destroy();                                                  // (a spectrum may still read the batch)
+    d->destroy();
     for (int k = 0; k < 2; ++k) {
         if (d->ev_gather[k]) (void)hipEventDestroy(d->ev_gather[k]);
-        if (d->ev_read[k]) (void)hipEventDestroy(d->ev_read[k]);
         d->carry[k].release(); d->batch[k].release(); d->starts[k].release(); d->starts_h[k].release();
     }
     d->stage.release();
@@ -91,7 +82,7 @@ extern "C" int csdr_distrib_set_lines_per_second(csdr_distrib *d, int lps) {    
 // a buffer a kernel in flight may still use is about to be replaced by a larger one
 static int distrib_grow(csdr_distrib *d, DevBuf<float2> &b, size_t n, int reader) {
     if (n <= b.cap) return CSDR_OK;
-    if (reader >= 0 && d->read_pending[reader]) { CSDR_HIP_TRY(hipEventSynchronize(d->ev_read[reader])); d->read_pending[reader] = false; }
+    if (reader >= 0) if (int rc = d->read[reader].sync()) return rc;
     CSDR_HIP_TRY(hipStreamSynchronize(d->st));
     return b.reserve(n);
 }
@@ -159,19 +150,15 @@ extern "C" int csdr_distrib_push(csdr_distrib *d, const float *iq, int iq_is_dev
         if (n_add > 0 && iq_is_dev) {
             // the block's producer: work on the boundary stream (the rule of csdr_spec_process for a device input) and, for a block of the ingest,
             // the transfer every stream of the context was made to wait for -- the spectrum's FFT lane stands for them
-            if (!(c->own_stream && !c->boundary_shared)) {
-                CSDR_HIP_TRY(hipEventRecord(d->ev_in, c->stream));
-                CSDR_HIP_TRY(hipStreamWaitEvent(d->st, d->ev_in, 0));
-            }
-            CSDR_HIP_TRY(hipEventRecord(d->ev_lane, c->lanes[LANE_FFT]));
-            CSDR_HIP_TRY(hipStreamWaitEvent(d->st, d->ev_lane, 0));
+            if (!(c->own_stream && !c->boundary_shared)) if (int rc = d->after_boundary()) return rc;
+            if (int rc = d->after(c->lanes[LANE_FFT])) return rc;
         } else if (n_add > 0) {
             if (int rc = distrib_grow(d, d->stage, (size_t)n_add, -1)) return rc;
             CSDR_HIP_TRY(hipMemcpyAsync(d->stage.p, iq, (size_t)n_add * sizeof(float2), hipMemcpyHostToDevice, d->st));
             block = d->stage.p;
         }
         if (n_lines > 0) CSDR_HIP_TRY(hipMemcpyAsync(d->starts[k].p, starts, (size_t)n_lines * sizeof(int), hipMemcpyHostToDevice, d->st));
-        if (d->read_pending[k]) { CSDR_HIP_TRY(hipStreamWaitEvent(d->st, d->ev_read[k], 0)); d->read_pending[k] = false; }      // the spectrum's reads of the batch being rewritten
+        if (int rc = d->read[k].wait(d->st)) return rc;                                 // the spectrum's reads of the batch being rewritten
         DistribArgs a{};
         a.carry_in = d->carry[d->carry_cur].p; a.block = block; a.lines = d->batch[k].p; a.carry_out = d->carry[out_c].p;
         a.starts = d->starts[k].p;
@@ -261,7 +248,6 @@ extern "C" int csdr_spec_process_distrib(csdr_spec *spec, csdr_distrib *d) {
         for (int l = 0; l < n && rc == CSDR_OK; ++l) rc = csdr_spec_process(spec, lines + 2 * (size_t)l * len, 1, 1, len, CSDR_SPEC_FIRST_FRAME);
     } else rc = csdr_spec_process(spec, lines, 1, n, len, len >= want ? CSDR_SPEC_FIRST_FRAME : CSDR_SPEC_LINES);
     // the distributor rewrites this batch at its second push from here: behind these reads (also those of a call that failed half-way)
-    CSDR_HIP_TRY(hipEventRecord(d->ev_read[k], c->lanes[LANE_FFT]));
-    d->read_pending[k] = true;
+    if (int rc2 = d->read[k].release(c->lanes[LANE_FFT])) return rc2;
     return rc;
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "stream_order.hpp"
 #include "design.hpp"
 #include "kernels_post.hpp"
 #include "kernels_chanfft.hpp"
@@ -130,8 +131,7 @@ struct csdr_bank {
     uint64_t seq = 0;
     hipEvent_t ev_fe_done[2] = {nullptr, nullptr}, ev_audio_done[2] = {nullptr, nullptr};
     bool audio_pending[2] = {false, false};
-    hipEvent_t ev_tables_read[2] = {nullptr, nullptr};      // behind the audio kernels of a batch: the device tables of its parity may be refetched (by the channelizer's stream)
-    bool tables_read_pending[2] = {false, false};
+    ReadGate tables_read[2];                 // behind the audio kernels of a batch: the device tables of its parity may be refetched (by the channelizer's stream)
     DevBuf<float> arms;
     DevBuf<ModemConsts> mconsts;
     PinBuf<char> tables_h[kStageRing];
@@ -158,18 +158,15 @@ struct csdr_bank {
     std::vector<GmskJob> gmsk_jobs_h;
     DevBuf<TableJob> tab_jobs;               // the table slots' launch records
     std::vector<TableJob> tab_jobs_h;
-    // a reader of the slots' resampled IQ that stays on the device (bank_iq_acquire / _release: the spectrum bank on its own stream); by parity of the
-    // batch it read.  Created at the first acquire: a bank nobody reads this way never has them
-    hipEvent_t ev_iq_ready = nullptr, ev_iq_read[2] = {nullptr, nullptr};
-    bool iq_read_pending[2] = {false, false};    // ev_iq_read[k] is recorded and not yet waited for
-    // the same for the slots' audio and scope taps (bank_audio_acquire / _release: the scope bank on its own stream).  SlotCfg::audio and ::scope are
-    // single-buffered: the NEXT execute's modem / audio lane waits for the reader
-    hipEvent_t ev_audio_ready = nullptr, ev_audio_read = nullptr;
-    bool audio_read_pending = false;             // ev_audio_read is recorded and not yet waited for
-    // the same for a batch's block plan in the device tables (bank_plan_release: the squelch bank), by parity of the batch that was read: the
-    // execute that refetches that copy of the tables -- the second one after -- waits for the reader
-    hipEvent_t ev_plan_read[2] = {nullptr, nullptr};
-    bool plan_read_pending[2] = {false, false};
+    // readers that stay on the device, each behind a gate of its own (stream_order.hpp); a bank nobody reads this way never has their events.
+    // The slots' resampled IQ (bank_iq_acquire / _release: the spectrum bank on its own stream), by parity of the batch that was read
+    ReadGate iq[2];
+    // the slots' audio and scope taps (bank_audio_acquire / _release: the scope bank on its own stream).  SlotCfg::audio and ::scope are
+    // single-buffered: the NEXT execute's modem / audio lane waits for the readers
+    ReadGate audio;
+    // a batch's block plan in the device tables (bank_plan_release: the squelch bank), by parity of the batch that was read: the execute that
+    // refetches that copy of the tables -- the second one after -- waits for the readers
+    ReadGate plan[2];
     uint64_t n_exec = 0;                         // csdr_bank_execute calls that got as far as clearing the slots' results: what a reader of "the last execute" was taken from
 };
 

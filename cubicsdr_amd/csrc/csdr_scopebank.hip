@@ -21,36 +21,27 @@ namespace {
 constexpr int kScbStage = 2;                 // page-locked staging sets of the plan
 }  // namespace
 
-struct csdr_scopebank {
-    csdr_ctx *ctx = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;      // boundary stream -> st (device frames of the caller), st -> boundary stream (csdr_scopebank_device_points)
+struct csdr_scopebank : SideStream, SlotOrder {         // (ev_in: device frames of the caller; ev_out: csdr_scopebank_device_points; the slot order of a call)
     bool ready = false, scope_on = true, spectrum_on = true;           // ctor :8-9
     int L = 0, max_slots = 0, max_frames = 0, max_n = 0, max_scope_samples = 1024;      // maxScopeSamples = DEFAULT_DMOD_FFT_SIZE (:13)
     float rate = 0.65f;                                // fft_average_rate (:10)
     bool last_wave = false, last_spec = false;         // which halves the last call produced
     std::vector<int> frames;                           // per slot: frames of the last call
-    std::vector<int> touched;                          // slots that got frames in the last call
     DevBuf<float2> tw4096;
     DevBuf<double> ma, maa;
     DevBuf<ScopeTrk> trk;
     DevBuf<float> wave_pts, spec_pts;
     DevBuf<ScopeMeta> wave_meta, spec_meta;
     StageRing<kScbStage> plan;                         // ScopeBankRun [runs] | ScopeBankJob [jobs] | float [samples of the host frames] of the call being run
-    // scratch of a call's planning
-    std::vector<int> n_jobs_of, job_at, cursor, run_slots;     // per slot: jobs of the call, its first job, the next one to fill; the slots that have jobs
-    std::vector<ScopeBankJob> jobs_h;
+    std::vector<ScopeBankJob> jobs_h;                  // scratch of a call's planning
     std::vector<csdr_scopebank_item> bank_items;
 };
 
 extern "C" int csdr_scopebank_create(csdr_ctx *ctx, csdr_scopebank **out) {
     DeviceScope dev__(ctx);
     if (!ctx || !out) return fail(CSDR_EINVAL, "null argument");
-    std::unique_ptr<csdr_scopebank> sb(new csdr_scopebank());
-    sb->ctx = ctx;
-    CSDR_HIP_TRY(hipStreamCreateWithFlags(&sb->st, hipStreamNonBlocking));
-    CSDR_HIP_TRY(hipEventCreateWithFlags(&sb->ev_in, hipEventDisableTiming));
-    CSDR_HIP_TRY(hipEventCreateWithFlags(&sb->ev_out, hipEventDisableTiming));
+    std::unique_ptr<csdr_scopebank, void (*)(csdr_scopebank *)> sb(new csdr_scopebank(), csdr_scopebank_destroy);
+    if (int rc = sb->create(ctx)) return rc;
     if (int rc = sb->plan.create()) return rc;
     *out = sb.release();
     return CSDR_OK;
@@ -59,9 +50,7 @@ extern "C" int csdr_scopebank_create(csdr_ctx *ctx, csdr_scopebank **out) {
 extern "C" void csdr_scopebank_destroy(csdr_scopebank *sb) {
     DeviceScope dev__(sb ? sb->ctx : nullptr);
     if (!sb) return;
-    if (sb->st) { (void)hipStreamSynchronize(sb->st); (void)hipStreamDestroy(sb->st); }
-    if (sb->ev_in) (void)hipEventDestroy(sb->ev_in);
-    if (sb->ev_out) (void)hipEventDestroy(sb->ev_out);
+    sb->destroy();
     sb->plan.destroy();
     sb->tw4096.release(); sb->ma.release(); sb->maa.release(); sb->trk.release();
     sb->wave_pts.release(); sb->spec_pts.release(); sb->wave_meta.release(); sb->spec_meta.release();
@@ -137,8 +126,8 @@ extern "C" int csdr_scopebank_reset_slot(csdr_scopebank *sb, int slot) {
 static bool scb_empty(const csdr_scopebank_item &it) { return it.frame.n == 0 || it.frame.data == nullptr; }     // no input at all (:53-61)
 
 // every check of a call, in front of anything that is enqueued or changed: the whole call is refused or none of it
-static int scb_check(const csdr_scopebank *sb, const csdr_scopebank_item *items, int n_items, std::vector<int> &n_jobs_of) {
-    n_jobs_of.assign((size_t)sb->max_slots, 0);
+static int scb_check(csdr_scopebank *sb, const csdr_scopebank_item *items, int n_items) {
+    sb->count_begin(sb->max_slots);
     for (int i = 0; i < n_items; ++i) {
         const csdr_scopebank_item &it = items[i];
         const csdr_scope_frame &f = it.frame;
@@ -148,47 +137,34 @@ static int scb_check(const csdr_scopebank *sb, const csdr_scopebank_item *items,
         if (f.channels != 1 && f.channels != 2) return fail(CSDR_EINVAL, "item %d: %d channels", i, f.channels);
         if (f.layout < 0 || f.layout > 2) return fail(CSDR_EINVAL, "item %d: layout %d", i, f.layout);
         if (f.n > sb->max_n) return fail(CSDR_ERANGE, "item %d: %d samples exceed max_samples %d", i, f.n, sb->max_n);
-        ++n_jobs_of[(size_t)it.slot];
+        sb->count_job(it.slot);
     }
     for (int s = 0; s < sb->max_slots; ++s)
-        if (n_jobs_of[(size_t)s] > sb->max_frames)
-            return fail(CSDR_ERANGE, "slot %d: %d frames in one call exceed max_frames %d", s, n_jobs_of[(size_t)s], sb->max_frames);
+        if (sb->n_jobs_of[(size_t)s] > sb->max_frames)
+            return fail(CSDR_ERANGE, "slot %d: %d frames in one call exceed max_frames %d", s, sb->n_jobs_of[(size_t)s], sb->max_frames);
     return CSDR_OK;
 }
 
-// the plan and the two launches of one call; `items` passed scb_check (n_jobs_of is its count).  data_is_dev: the frames lie in device memory the
+// the plan and the two launches of one call; `items` passed scb_check (which counted the jobs per slot).  data_is_dev: the frames lie in device memory the
 // caller produced on the boundary stream; bank: they are that bank's audio / scope taps -- acquired here, where the call can no longer be refused,
 // released behind the kernels
 static int scb_run(csdr_scopebank *sb, const csdr_scopebank_item *items, int n_items, bool data_is_dev, csdr_bank *bank = nullptr) {
-    size_t n_jobs = 0, host_floats = 0;
-    sb->run_slots.clear();
-    sb->job_at.assign((size_t)sb->max_slots, 0);
-    for (int s = 0; s < sb->max_slots; ++s)
-        if (sb->n_jobs_of[(size_t)s]) { sb->run_slots.push_back(s); sb->job_at[(size_t)s] = (int)n_jobs; n_jobs += (size_t)sb->n_jobs_of[(size_t)s]; }
+    const size_t n_jobs = sb->order();
+    size_t host_floats = 0;
     if (!data_is_dev)
         for (int i = 0; i < n_items; ++i) if (!scb_empty(items[i])) host_floats += (size_t)items[i].frame.n;
     // ---- commit the host state; from here on the call is enqueued
-    for (int s : sb->touched) sb->frames[(size_t)s] = 0;
-    sb->touched = sb->run_slots;
-    for (int s : sb->run_slots) sb->frames[(size_t)s] = sb->n_jobs_of[(size_t)s];
+    sb->commit([&](int s) { sb->frames[(size_t)s] = 0; }, [&](int s) { sb->frames[(size_t)s] = sb->n_jobs_of[(size_t)s]; });
     sb->last_wave = sb->scope_on; sb->last_spec = sb->spectrum_on;
     if (n_jobs == 0 || (!sb->scope_on && !sb->spectrum_on)) return CSDR_OK;
     if (bank) { if (int rc = bank_audio_acquire(bank, sb->st)) return rc; }
-    else if (data_is_dev) {
-        CSDR_HIP_TRY(hipEventRecord(sb->ev_in, sb->ctx->stream));
-        CSDR_HIP_TRY(hipStreamWaitEvent(sb->st, sb->ev_in, 0));
-    }
+    else if (data_is_dev) { if (int rc = sb->after_boundary()) return rc; }
     const size_t n_runs = sb->run_slots.size();
-    const size_t off_jobs = n_runs * sizeof(ScopeBankRun), off_data = off_jobs + n_jobs * sizeof(ScopeBankJob);
+    const size_t off_jobs = sb->run_bytes(), off_data = off_jobs + n_jobs * sizeof(ScopeBankJob);
     const size_t bytes = off_data + host_floats * sizeof(float);
     if (int rc = sb->plan.begin(sb->st, bytes)) return rc;           // the one host wait of a call
-    ScopeBankRun *runs_h = reinterpret_cast<ScopeBankRun *>(sb->plan.host());
-    for (size_t r = 0; r < n_runs; ++r) {
-        const int s = sb->run_slots[r];
-        runs_h[r] = ScopeBankRun{s, sb->job_at[(size_t)s], sb->n_jobs_of[(size_t)s], 0};
-    }
+    sb->fill_runs(sb->plan.host());
     sb->jobs_h.resize(n_jobs);
-    sb->cursor = sb->job_at;
     float *data_h = reinterpret_cast<float *>(sb->plan.host() + off_data);
     const float *data_d = reinterpret_cast<const float *>(sb->plan.device() + off_data);
     size_t at = 0;
@@ -196,7 +172,7 @@ static int scb_run(csdr_scopebank *sb, const csdr_scopebank_item *items, int n_i
         const csdr_scopebank_item &it = items[i];
         if (scb_empty(it)) continue;
         const csdr_scope_frame &f = it.frame;
-        const int j = sb->cursor[(size_t)it.slot]++;
+        const int j = (int)sb->next_job(it.slot);
         ScopeBankJob &jb = sb->jobs_h[(size_t)j];
         memset(&jb, 0, sizeof jb);
         ScopeFrame &d = jb.fr;
@@ -241,7 +217,7 @@ extern "C" int csdr_scopebank_process(csdr_scopebank *sb, const csdr_scopebank_i
     DeviceScope dev__(sb ? sb->ctx : nullptr);
     if (!sb || !sb->ready) return fail(CSDR_ESTATE, "scope bank not set up");
     if (n_items < 0 || (n_items > 0 && !items)) return fail(CSDR_EINVAL, "bad items");
-    if (int rc = scb_check(sb, items, n_items, sb->n_jobs_of)) return rc;
+    if (int rc = scb_check(sb, items, n_items)) return rc;
     return scb_run(sb, items, n_items, data_is_dev != 0);
 }
 
@@ -263,7 +239,7 @@ extern "C" int csdr_scopebank_process_bank(csdr_scopebank *sb, csdr_bank *bank) 
         if (int rc = csdr_bank_scope_frame(bank, si, &it.frame)) return rc;
         if (!scb_empty(it)) sb->bank_items.push_back(it);
     }
-    if (int rc = scb_check(sb, sb->bank_items.data(), (int)sb->bank_items.size(), sb->n_jobs_of)) return rc;
+    if (int rc = scb_check(sb, sb->bank_items.data(), (int)sb->bank_items.size())) return rc;
     return scb_run(sb, sb->bank_items.data(), (int)sb->bank_items.size(), true, sb->bank_items.empty() ? nullptr : bank);
 }
 
@@ -300,8 +276,7 @@ extern "C" int csdr_scopebank_device_points(csdr_scopebank *sb, int slot, int wh
     DeviceScope dev__(sb ? sb->ctx : nullptr);
     if (!sb || !sb->ready) return fail(CSDR_ESTATE, "scope bank not set up");
     if (!dev || slot < 0 || slot >= sb->max_slots || which < 0 || which > 1) return fail(CSDR_EINVAL, "bad argument");
-    CSDR_HIP_TRY(hipEventRecord(sb->ev_out, sb->st));     // whatever the caller enqueues on the boundary stream next reads the finished items
-    CSDR_HIP_TRY(hipStreamWaitEvent(sb->ctx->stream, sb->ev_out, 0));
+    if (int rc = sb->hand_over()) return rc;              // whatever the caller enqueues on the boundary stream next reads the finished items
     const size_t fo = (size_t)slot * (size_t)sb->max_frames;
     const int stride = which ? sb->L : 2 * sb->max_n;
     *dev = (which ? sb->spec_pts.p : sb->wave_pts.p) + fo * (size_t)stride;

@@ -77,8 +77,7 @@ struct csdr_spec {
     bool fused_ok = false;                   // N = 2^17: the 512 x 256 chain with the averaging fused into the row pass exists (kernels_spec3.hpp)
     bool fused_now = false;                  // ... and this batch takes it (full-span view)
     // a reader of `points` that stays on the device (spec_points_acquire / _release: the waterfall's quantiser on its own stream)
-    hipEvent_t ev_points_ready = nullptr, ev_points_read = nullptr;
-    bool points_reader = false;              // ev_points_read is recorded and not yet waited for
+    ReadGate points_gate;
 };
 
 extern "C" int csdr_spec_create(csdr_ctx *ctx, csdr_spec **out) {
@@ -87,11 +86,9 @@ extern "C" int csdr_spec_create(csdr_ctx *ctx, csdr_spec **out) {
     std::unique_ptr<csdr_spec> s(new csdr_spec());
     s->ctx = ctx;
     for (int k = 0; k < 2; ++k) {
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&s->ev_fft_done[k], hipEventDisableTiming));
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&s->ev_avg_done[k], hipEventDisableTiming));
+        if (int rc = order_event(&s->ev_fft_done[k])) return rc;
+        if (int rc = order_event(&s->ev_avg_done[k])) return rc;
     }
-    CSDR_HIP_TRY(hipEventCreateWithFlags(&s->ev_points_ready, hipEventDisableTiming));
-    CSDR_HIP_TRY(hipEventCreateWithFlags(&s->ev_points_read, hipEventDisableTiming));
     *out = s.release();
     return CSDR_OK;
 }
@@ -99,13 +96,11 @@ extern "C" void csdr_spec_destroy(csdr_spec *s) {
     DeviceScope dev__(s ? s->ctx : nullptr);
     if (!s) return;
     (void)s->ctx->sync_all();
-    if (s->points_reader) (void)hipEventSynchronize(s->ev_points_read);      // (a reader on a stream that is not the context's)
+    s->points_gate.destroy();                // (host-waits for a reader on a stream that is not the context's)
     for (int k = 0; k < 2; ++k) {
         if (s->ev_fft_done[k]) (void)hipEventDestroy(s->ev_fft_done[k]);
         if (s->ev_avg_done[k]) (void)hipEventDestroy(s->ev_avg_done[k]);
     }
-    if (s->ev_points_ready) (void)hipEventDestroy(s->ev_points_ready);
-    if (s->ev_points_read) (void)hipEventDestroy(s->ev_points_read);
     s->tw4096.release(); s->tw_hi.release(); s->tw_lo.release(); s->tmp.release(); s->carry.release();
     s->blue_w.release(); s->blue_B.release(); s->blue_a.release(); s->blue_b.release(); s->twL_hi.release(); s->twL_lo.release();
     s->stage_in.release(); s->raw.release(); s->mag.release(); s->ext_w.release(); s->ext.release(); s->pairsum.release(); s->first_b.release(); s->points.release();
@@ -129,7 +124,7 @@ extern "C" int csdr_spec_setup(csdr_spec *s, int fft_size, int max_frames) {
     const int N = 2 * fft_size;                                      // SPECTRUM_VZM 2, SpectrumVisualProcessor.h:11, .cpp:145
     if (N > (1 << 22) || (npot && 2 * (int64_t)N - 1 > (1 << 22))) return fail(CSDR_EUNSUPPORTED, "internal FFT of %d points exceeds 2^22%s", N, npot ? " (the chirp-z convolution of a size that is not a power of two is twice as long)" : "");
     if (int rc = s->ctx->sync_all()) return rc;
-    if (s->points_reader) { CSDR_HIP_TRY(hipEventSynchronize(s->ev_points_read)); s->points_reader = false; }     // the buffers below may be reallocated
+    if (int rc = s->points_gate.sync()) return rc;       // the buffers below may be reallocated
     s->ready = false;
     s->seq = 0; s->avg_pending[0] = s->avg_pending[1] = false; s->tmp_reader = -1;
     SpecGeom &g = s->g;
@@ -704,10 +699,7 @@ extern "C" int csdr_spec_process(csdr_spec *s, const float *iq, int iq_is_dev, i
     DeviceScope dev__(s ? s->ctx : nullptr);
     if (!s || !s->ready) return fail(CSDR_ESTATE, "spec not set up");
     if (!iq || n_blocks <= 0 || block_len <= 0) return fail(CSDR_EINVAL, "bad block arguments");
-    if (s->points_reader) {                  // a device-side reader of the previous points (spec_points_release): the averaging lane rewrites them behind it
-        CSDR_HIP_TRY(hipStreamWaitEvent(s->ctx->lanes[LANE_AVG], s->ev_points_read, 0));
-        s->points_reader = false;
-    }
+    if (int rc = s->points_gate.wait(s->ctx->lanes[LANE_AVG])) return rc;       // device-side readers of the previous points (spec_points_release): the averaging lane rewrites them behind them
     if (s->is_view) {
         if (n_blocks != 1) return fail(CSDR_EINVAL, "the zoomed view takes one process() input per call");
         return spec_process_view(s, iq, iq_is_dev, block_len);
@@ -791,18 +783,13 @@ static void spec_hide_dc(const csdr_spec *s, float *pts) {
 
 int spec_points_acquire(csdr_spec *s, hipStream_t reader, SpecPointsRef *out) {
     if (!s || !s->ready || !out) return fail(CSDR_ESTATE, "spec not set up");
-    CSDR_HIP_TRY(hipEventRecord(s->ev_points_ready, s->ctx->lanes[LANE_AVG]));
-    CSDR_HIP_TRY(hipStreamWaitEvent(reader, s->ev_points_ready, 0));
+    if (int rc = s->points_gate.acquire(s->ctx->lanes[LANE_AVG], reader)) return rc;
     out->ctx = s->ctx; out->points = s->points.p; out->F = s->g.F; out->frames = s->nf_last;
     out->dc = s->hide_dc ? hide_dc_span(s->center_freq, s->input_freq, s->bandwidth, s->g.F) : HideDcSpan();
     return CSDR_OK;
 }
 csdr_ctx *spec_ctx(const csdr_spec *s) { return s ? s->ctx : nullptr; }
-int spec_points_release(csdr_spec *s, hipStream_t reader) {
-    CSDR_HIP_TRY(hipEventRecord(s->ev_points_read, reader));
-    s->points_reader = true;
-    return CSDR_OK;
-}
+int spec_points_release(csdr_spec *s, hipStream_t reader) { return s->points_gate.release(reader); }
 
 // The device keeps only the y of every display point (the x of point i is i / F in every frame, SpectrumVisualProcessor.cpp:562: half of
 // the display kernel's stores and of the fetch's transfer were that constant).  pts[F .. 2F) holds the F values just fetched: interleave

@@ -18,24 +18,16 @@ static_assert(sizeof(csdr_specbank_item) == 24 && offsetof(csdr_specbank_item, i
 struct csdr_specbank : SbBank<SbSlot, SpecBankJob> {
     static constexpr const char *kName = "spectrum bank";
     std::vector<csdr_specbank_item> bank_items;
-    // a reader of `points` that stays on the device (specbank_points_acquire / _release: the waterfall bank's quantiser on its own stream).  Created
-    // at the first acquire: a spectrum bank nobody reads this way never has them
-    hipEvent_t ev_points_ready = nullptr, ev_points_read = nullptr;
-    bool points_reader = false;                        // ev_points_read is recorded and not yet waited for
+    ReadGate points_gate;                              // readers of `points` that stay on the device (specbank_points_acquire / _release: the waterfall bank's quantiser on its own stream)
 };
 
-// whatever rewrites the points comes behind the reader that was handed them (one test, untaken while nobody reads this way)
-static int sb_wait_reader(csdr_specbank *sb) {
-    if (!sb->points_reader) return CSDR_OK;
-    CSDR_HIP_TRY(hipStreamWaitEvent(sb->st, sb->ev_points_read, 0));
-    sb->points_reader = false;
-    return CSDR_OK;
-}
+// whatever rewrites the points comes behind the readers that were handed them
+static int sb_wait_reader(csdr_specbank *sb) { return sb->points_gate.wait(sb->st); }
 
 extern "C" int csdr_specbank_create(csdr_ctx *ctx, csdr_specbank **out) {
     DeviceScope dev__(ctx);
     if (!ctx || !out) return fail(CSDR_EINVAL, "null argument");
-    std::unique_ptr<csdr_specbank> sb(new csdr_specbank());
+    std::unique_ptr<csdr_specbank, void (*)(csdr_specbank *)> sb(new csdr_specbank(), csdr_specbank_destroy);
     if (int rc = sb->create_base(ctx)) return rc;
     *out = sb.release();
     return CSDR_OK;
@@ -44,9 +36,8 @@ extern "C" int csdr_specbank_create(csdr_ctx *ctx, csdr_specbank **out) {
 extern "C" void csdr_specbank_destroy(csdr_specbank *sb) {
     DeviceScope dev__(sb ? sb->ctx : nullptr);
     if (!sb) return;
+    sb->points_gate.destroy();                           // (host-waits for a reader on a stream that is not the object's)
     sb->destroy_base();
-    if (sb->ev_points_ready) (void)hipEventDestroy(sb->ev_points_ready);
-    if (sb->ev_points_read) (void)hipEventDestroy(sb->ev_points_read);
     delete sb;
 }
 
@@ -98,7 +89,7 @@ extern "C" int csdr_specbank_reset_slot(csdr_specbank *sb, int slot) {
 static int sb_run(csdr_specbank *sb, const csdr_specbank_item *items, int n_items, bool any_dev, csdr_bank *bank = nullptr) {
     const int Fi = sb->Fi;
     // ---- plan on copies: a refused call leaves every slot as it was
-    sb->count_begin();
+    sb->count_begin(sb->max_slots);
     size_t n_jobs = 0, host_samples = 0;
     for (int i = 0; i < n_items; ++i) {
         const csdr_specbank_item &it = items[i];
@@ -107,7 +98,7 @@ static int sb_run(csdr_specbank *sb, const csdr_specbank_item *items, int n_item
         ++n_jobs;
         if (!it.is_dev) host_samples += (size_t)std::min(it.n, Fi);
     }
-    sb->order_jobs(n_jobs);
+    sb->order_jobs();
     for (int i = 0; i < n_items; ++i) {
         const csdr_specbank_item &it = items[i];
         if (it.n == 0) continue;
@@ -124,10 +115,7 @@ static int sb_run(csdr_specbank *sb, const csdr_specbank_item *items, int n_item
     if (n_jobs == 0) return CSDR_OK;
     if (int rc = sb_wait_reader(sb)) return rc;
     if (bank) if (int rc = bank_iq_acquire(bank, sb->st)) return rc;
-    if (any_dev) {
-        CSDR_HIP_TRY(hipEventRecord(sb->ev_in, sb->ctx->stream));
-        CSDR_HIP_TRY(hipStreamWaitEvent(sb->st, sb->ev_in, 0));
-    }
+    if (any_dev) if (int rc = sb->after_boundary()) return rc;
     if (int rc = sb->stage_inputs(items, n_items, host_samples)) return rc;
     SpecBankArgs a{};
     if (int rc = sb->upload_plan(&a.runs, &a.jobs)) return rc;
@@ -191,17 +179,8 @@ extern "C" int csdr_specbank_device_points(csdr_specbank *sb, int slot, const fl
 // ---- the points for a reader that stays on the device (csdr_objects.hpp) ----
 int specbank_points_acquire(csdr_specbank *sb, hipStream_t reader, SpecBankPointsRef *out) {
     if (!sb || !sb->ready || !out) return fail(CSDR_ESTATE, "spectrum bank not set up");
-    if (!sb->ev_points_ready) {
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&sb->ev_points_ready, hipEventDisableTiming));
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&sb->ev_points_read, hipEventDisableTiming));
-    }
-    CSDR_HIP_TRY(hipEventRecord(sb->ev_points_ready, sb->st));
-    CSDR_HIP_TRY(hipStreamWaitEvent(reader, sb->ev_points_ready, 0));
+    if (int rc = sb->points_gate.acquire(sb->st, reader)) return rc;
     out->ctx = sb->ctx; out->points = sb->points.p; out->F = sb->F; out->max_slots = sb->max_slots; out->max_frames = sb->max_frames;
     return CSDR_OK;
 }
-int specbank_points_release(csdr_specbank *sb, hipStream_t reader) {
-    CSDR_HIP_TRY(hipEventRecord(sb->ev_points_read, reader));
-    sb->points_reader = true;
-    return CSDR_OK;
-}
+int specbank_points_release(csdr_specbank *sb, hipStream_t reader) { return sb->points_gate.release(reader); }

@@ -20,10 +20,7 @@ constexpr int kSqStage = 2;                  // page-locked staging sets of the 
 struct SqSettings { bool enabled = false, muted = false; int record = CSDR_RECORD_SILENCE; float level_db = 0.0f; };     // squelchEnabled, muted, the sink's option, squelchLevel
 }  // namespace
 
-struct csdr_squelch {
-    csdr_ctx *ctx = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;      // boundary stream -> st (device audio of the caller), st -> boundary stream (csdr_squelch_device_items)
+struct csdr_squelch : SideStream {                     // (ev_in: device audio of the caller; ev_out: csdr_squelch_device_items)
     int max_slots = 0, max_blocks = 0;
     std::vector<SqSettings> set;
     std::vector<int> blocks;                           // per slot: blocks stepped by the last process
@@ -52,25 +49,22 @@ extern "C" int csdr_squelch_create(csdr_ctx *ctx, int max_slots, int max_blocks,
     if (!ctx || !out) return fail(CSDR_EINVAL, "null argument");
     if (max_slots < 1 || max_slots > kSqMaxSlots) return fail(CSDR_EINVAL, "max_slots %d: 1 .. %d", max_slots, kSqMaxSlots);
     if (max_blocks < 1) return fail(CSDR_EINVAL, "max_blocks %d", max_blocks);
-    std::unique_ptr<csdr_squelch> sq(new csdr_squelch());
-    auto undo = [&](int rc) { csdr_squelch_destroy(sq.release()); return rc; };
-    sq->ctx = ctx; sq->max_slots = max_slots; sq->max_blocks = max_blocks;
-    if (hipStreamCreateWithFlags(&sq->st, hipStreamNonBlocking) != hipSuccess) return undo(fail(CSDR_EHIP, "hipStreamCreateWithFlags failed"));
-    if (hipEventCreateWithFlags(&sq->ev_in, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&sq->ev_out, hipEventDisableTiming) != hipSuccess)
-        return undo(fail(CSDR_EHIP, "hipEventCreateWithFlags failed"));
-    if (int rc = sq->plan.create()) return undo(rc);
+    std::unique_ptr<csdr_squelch, void (*)(csdr_squelch *)> sq(new csdr_squelch(), csdr_squelch_destroy);
+    sq->max_slots = max_slots; sq->max_blocks = max_blocks;
+    if (int rc = sq->create(ctx)) return rc;
+    if (int rc = sq->plan.create()) return rc;
     const size_t S = (size_t)max_slots, SB = S * (size_t)max_blocks;
-    if (int rc = sq->state.reserve(S)) return undo(rc);
-    if (int rc = sq->items.reserve(SB)) return undo(rc);
-    if (int rc = sq->flags.reserve(SB)) return undo(rc);
-    if (int rc = sq->recs.reserve(SB)) return undo(rc);
-    if (int rc = sq->totals.reserve(S)) return undo(rc);
-    if (int rc = sq->pack.reserve(S + 1)) return undo(rc);
-    if (int rc = sq->fresh.reserve(1)) return undo(rc);
+    if (int rc = sq->state.reserve(S)) return rc;
+    if (int rc = sq->items.reserve(SB)) return rc;
+    if (int rc = sq->flags.reserve(SB)) return rc;
+    if (int rc = sq->recs.reserve(SB)) return rc;
+    if (int rc = sq->totals.reserve(S)) return rc;
+    if (int rc = sq->pack.reserve(S + 1)) return rc;
+    if (int rc = sq->fresh.reserve(1)) return rc;
     sq->fresh.p[0] = SquelchState{-100.0f, -30.0f, 30.0f, 0};                           // DemodulatorThread ctor (:20-27)
     std::vector<SquelchState> all(S, sq->fresh.p[0]);
-    if (hipMemcpy(sq->state.p, all.data(), S * sizeof(SquelchState), hipMemcpyHostToDevice) != hipSuccess) return undo(fail(CSDR_EHIP, "hipMemcpy failed"));
-    if (hipMemset(sq->flags.p, 0, SB) != hipSuccess) return undo(fail(CSDR_EHIP, "hipMemset failed"));
+    CSDR_HIP_TRY(hipMemcpy(sq->state.p, all.data(), S * sizeof(SquelchState), hipMemcpyHostToDevice));
+    CSDR_HIP_TRY(hipMemset(sq->flags.p, 0, SB));
     sq->set.assign(S, SqSettings{});
     sq->blocks.assign(S, 0);
     sq->flags_h.assign(SB, 0);
@@ -81,9 +75,7 @@ extern "C" int csdr_squelch_create(csdr_ctx *ctx, int max_slots, int max_blocks,
 extern "C" void csdr_squelch_destroy(csdr_squelch *sq) {
     DeviceScope dev__(sq ? sq->ctx : nullptr);
     if (!sq) return;
-    if (sq->st) { (void)hipStreamSynchronize(sq->st); (void)hipStreamDestroy(sq->st); }
-    if (sq->ev_in) (void)hipEventDestroy(sq->ev_in);
-    if (sq->ev_out) (void)hipEventDestroy(sq->ev_out);
+    sq->destroy();
     sq->plan.destroy();
     sq->state.release(); sq->items.release(); sq->flags.release(); sq->recs.release(); sq->totals.release(); sq->pack.release(); sq->pcm.release();
     sq->fresh.release();
@@ -162,10 +154,7 @@ static int sq_run(csdr_squelch *sq, const csdr_squelch_input *const *in, csdr_ba
     CSDR_HIP_TRY(hipMemsetAsync(sq->totals.p, 0, S * sizeof(int32_t), sq->st));
     if (n_runs == 0) return CSDR_OK;
     if (bank) { if (int rc = bank_audio_acquire(bank, sq->st)) return rc; }
-    else if (any_dev) {
-        CSDR_HIP_TRY(hipEventRecord(sq->ev_in, sq->ctx->stream));
-        CSDR_HIP_TRY(hipStreamWaitEvent(sq->st, sq->ev_in, 0));
-    }
+    else if (any_dev) { if (int rc = sq->after_boundary()) return rc; }
     const size_t off_blocks = n_runs * sizeof(SquelchRun), off_audio = off_blocks + n_blocks * sizeof(csdr_squelch_block);
     const size_t bytes = off_audio + host_floats * sizeof(float);
     if (int rc = sq->plan.begin(sq->st, bytes)) return rc;                             // the one host wait of a call
@@ -333,8 +322,7 @@ extern "C" int csdr_squelch_device_items(csdr_squelch *sq, const csdr_squelch_it
     DeviceScope dev__(sq ? sq->ctx : nullptr);
     if (!sq) return fail(CSDR_ESTATE, "squelch bank is null");
     if (!dev) return fail(CSDR_EINVAL, "null argument");
-    CSDR_HIP_TRY(hipEventRecord(sq->ev_out, sq->st));      // whatever the caller enqueues on the boundary stream next reads the finished items
-    CSDR_HIP_TRY(hipStreamWaitEvent(sq->ctx->stream, sq->ev_out, 0));
+    if (int rc = sq->hand_over()) return rc;               // whatever the caller enqueues on the boundary stream next reads the finished items
     *dev = sq->items.p;
     if (stride_items) *stride_items = sq->max_blocks;
     return CSDR_OK;

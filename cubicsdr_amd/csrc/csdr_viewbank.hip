@@ -64,7 +64,7 @@ struct csdr_viewbank : SbBank<VbSlot, ViewBankJob> {
 extern "C" int csdr_viewbank_create(csdr_ctx *ctx, csdr_viewbank **out) {
     DeviceScope dev__(ctx);
     if (!ctx || !out) return fail(CSDR_EINVAL, "null argument");
-    std::unique_ptr<csdr_viewbank> vb(new csdr_viewbank());
+    std::unique_ptr<csdr_viewbank, void (*)(csdr_viewbank *)> vb(new csdr_viewbank(), csdr_viewbank_destroy);
     if (int rc = vb->create_base(ctx)) return rc;
     *out = vb.release();
     return CSDR_OK;
@@ -187,7 +187,7 @@ static void vb_view_map(int F, int64_t bandwidth, int64_t resample_bw, std::vect
 static int vb_run(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_items, bool any_dev, csdr_post *post = nullptr) {
     const int Fi = vb->Fi, F = vb->F;
     // ---- plan on copies: a refused call leaves every slot as it was
-    vb->count_begin();
+    vb->count_begin(vb->max_slots);
     size_t n_jobs = 0;
     for (int i = 0; i < n_items; ++i) {
         const csdr_viewbank_item &it = items[i];
@@ -197,7 +197,7 @@ static int vb_run(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_item
         vb->count_job(it.slot);
         ++n_jobs;
     }
-    vb->order_jobs(n_jobs);
+    vb->order_jobs();
     vb->job_map.assign(n_jobs, -1);
     vb->new_maps.clear();
     size_t host_samples = 0;
@@ -299,13 +299,10 @@ static int vb_run(csdr_viewbank *vb, const csdr_viewbank_item *items, int n_item
     if (post) {      // the rows of the channelizer's batch are complete
         const int pk = post->cur;
         csdr_ctx *c = post->ctx;
-        if (c->same(LANE_POST, LANE_FE)) { CSDR_HIP_TRY(hipEventRecord(vb->ev_in, c->lanes[LANE_POST])); CSDR_HIP_TRY(hipStreamWaitEvent(st, vb->ev_in, 0)); }    // (ev_ready is recorded only between two streams)
+        if (c->same(LANE_POST, LANE_FE)) { if (int rc = vb->after(c->lanes[LANE_POST])) return rc; }    // (ev_ready is recorded only between two streams)
         else CSDR_HIP_TRY(hipStreamWaitEvent(st, post->ev_ready[pk], 0));
     }
-    if (any_dev) {
-        CSDR_HIP_TRY(hipEventRecord(vb->ev_in, vb->ctx->stream));
-        CSDR_HIP_TRY(hipStreamWaitEvent(st, vb->ev_in, 0));
-    }
+    if (any_dev) if (int rc = vb->after_boundary()) return rc;
     // resamplers designed since the last upload
     if (vb->cfgs_on_device < vb->cfgs_h.size()) {
         const size_t n = vb->cfgs_h.size(), per = (size_t)kArms * kArmTaps;

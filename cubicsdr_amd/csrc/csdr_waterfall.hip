@@ -12,10 +12,7 @@
 
 using namespace csdr;
 
-struct csdr_waterfall {
-    csdr_ctx *ctx = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;      // boundary stream -> st (device points of the caller), st -> boundary stream (csdr_waterfall_device_rgba)
+struct csdr_waterfall : SideStream {                   // (ev_in: device points of the caller; ev_out: csdr_waterfall_device_rgba)
     bool ready = false;
     int fft_size = 0, half = 0, pitch = 0, lines = 0, max_pending = 0;
     // WaterfallPanel's state
@@ -41,11 +38,8 @@ struct csdr_waterfall {
 extern "C" int csdr_waterfall_create(csdr_ctx *ctx, csdr_waterfall **out) {
     DeviceScope dev__(ctx);
     if (!ctx || !out) return fail(CSDR_EINVAL, "null argument");
-    std::unique_ptr<csdr_waterfall> w(new csdr_waterfall());
-    w->ctx = ctx;
-    CSDR_HIP_TRY(hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking));
-    CSDR_HIP_TRY(hipEventCreateWithFlags(&w->ev_in, hipEventDisableTiming));
-    CSDR_HIP_TRY(hipEventCreateWithFlags(&w->ev_out, hipEventDisableTiming));
+    std::unique_ptr<csdr_waterfall, void (*)(csdr_waterfall *)> w(new csdr_waterfall(), csdr_waterfall_destroy);
+    if (int rc = w->create(ctx)) return rc;
     if (int rc = w->table.reserve(256)) return rc;
     if (int rc = wf_upload_grey_table(w->st, w->table.p)) return rc;        // before any csdr_waterfall_set_gradient
     *out = w.release();
@@ -55,9 +49,7 @@ extern "C" int csdr_waterfall_create(csdr_ctx *ctx, csdr_waterfall **out) {
 extern "C" void csdr_waterfall_destroy(csdr_waterfall *w) {
     DeviceScope dev__(w ? w->ctx : nullptr);
     if (!w) return;
-    if (w->st) { (void)hipStreamSynchronize(w->st); (void)hipStreamDestroy(w->st); }
-    if (w->ev_in) (void)hipEventDestroy(w->ev_in);
-    if (w->ev_out) (void)hipEventDestroy(w->ev_out);
+    w->destroy();
     w->points.release(); w->stage.release(); w->pend.release(); w->ring.release(); w->table.release(); w->image.release(); w->taps.dev.release(); w->view.release();
     delete w;
 }
@@ -146,8 +138,7 @@ extern "C" int csdr_waterfall_step(csdr_waterfall *w, const float *points, int i
         if (!w->tex_init || w->lines_buffered + (int64_t)n_lines <= w->max_pending) {      // (a refused call moves nothing)
             if (is_dev) {
                 if ((uintptr_t)points & 3) return fail(CSDR_EINVAL, "device points must be 4-byte aligned");
-                CSDR_HIP_TRY(hipEventRecord(w->ev_in, w->ctx->stream));                      // the caller produced them on the boundary stream
-                CSDR_HIP_TRY(hipStreamWaitEvent(w->st, w->ev_in, 0));
+                if (int rc = w->after_boundary()) return rc;                                 // the caller produced them on the boundary stream
             } else {
                 const size_t n = (size_t)n_lines * (size_t)n_floats_per_line;
                 if (n > w->stage.cap) CSDR_HIP_TRY(hipStreamSynchronize(w->st));             // (a kernel may still read the buffer being replaced)
@@ -241,7 +232,7 @@ extern "C" int csdr_waterfall_device_rgba(csdr_waterfall *w, const uint8_t **dev
     DeviceScope dev__(w ? w->ctx : nullptr);
     if (!w || !dev) return fail(CSDR_EINVAL, "null argument");
     if (!w->ready || w->image_pixels == 0) return fail(CSDR_ESTATE, "nothing rendered yet (csdr_waterfall_fetch_rgba)");
-    if (int rc = wf_hand_over(w->ev_out, w->st, w->ctx->stream)) return rc;
+    if (int rc = w->hand_over()) return rc;
     *dev = reinterpret_cast<const uint8_t *>(w->image.p);
     return CSDR_OK;
 }
@@ -328,7 +319,7 @@ extern "C" int csdr_waterfall_device_view(csdr_waterfall *w, const uint8_t **dev
     DeviceScope dev__(w ? w->ctx : nullptr);
     if (!w || !dev) return fail(CSDR_EINVAL, "null argument");
     if (!w->ready || w->view_w == 0) return fail(CSDR_ESTATE, "nothing rendered yet (csdr_waterfall_render_view)");
-    if (int rc = wf_hand_over(w->ev_out, w->st, w->ctx->stream)) return rc;
+    if (int rc = w->hand_over()) return rc;
     *dev = reinterpret_cast<const uint8_t *>(w->view.p);
     if (width) *width = w->view_w;
     if (height) *height = w->view_h;

@@ -42,10 +42,7 @@ constexpr int kWbStage = 2;                            // page-locked staging se
 constexpr int kWbPeakRows = 8;                         // wfb_view_peak: image rows to a workgroup at most (16 KB of LDS at half 2048)
 }  // namespace
 
-struct csdr_wfbank {
-    csdr_ctx *ctx = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;      // boundary stream -> st (device lines of the caller), st -> boundary stream (csdr_wfbank_device_view)
+struct csdr_wfbank : SideStream {                      // (ev_in: device lines of the caller; ev_out: csdr_wfbank_device_view)
     bool ready = false;
     int fft_size = 0, half = 0, pitch = 0, lines = 0, max_slots = 0, max_pending = 0;
     int fp = 0;                                        // floats of one copy of a slot's points: fft_size rounded up to 16 bytes
@@ -76,11 +73,8 @@ static int wb_block(int items) { return std::min(kWfThreads, (items + 63) / 64 *
 extern "C" int csdr_wfbank_create(csdr_ctx *ctx, csdr_wfbank **out) {
     DeviceScope dev__(ctx);
     if (!ctx || !out) return fail(CSDR_EINVAL, "null argument");
-    std::unique_ptr<csdr_wfbank> w(new csdr_wfbank());
-    w->ctx = ctx;
-    CSDR_HIP_TRY(hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking));
-    CSDR_HIP_TRY(hipEventCreateWithFlags(&w->ev_in, hipEventDisableTiming));
-    CSDR_HIP_TRY(hipEventCreateWithFlags(&w->ev_out, hipEventDisableTiming));
+    std::unique_ptr<csdr_wfbank, void (*)(csdr_wfbank *)> w(new csdr_wfbank(), csdr_wfbank_destroy);
+    if (int rc = w->create(ctx)) return rc;
     if (int rc = w->plan.create()) return rc;
     if (int rc = w->table.reserve(256)) return rc;
     if (int rc = wf_upload_grey_table(w->st, w->table.p)) return rc;        // before any csdr_wfbank_set_gradient
@@ -91,9 +85,7 @@ extern "C" int csdr_wfbank_create(csdr_ctx *ctx, csdr_wfbank **out) {
 extern "C" void csdr_wfbank_destroy(csdr_wfbank *w) {
     DeviceScope dev__(w ? w->ctx : nullptr);
     if (!w) return;
-    if (w->st) { (void)hipStreamSynchronize(w->st); (void)hipStreamDestroy(w->st); }
-    if (w->ev_in) (void)hipEventDestroy(w->ev_in);
-    if (w->ev_out) (void)hipEventDestroy(w->ev_out);
+    w->destroy();
     w->plan.destroy();
     w->points.release(); w->pend.release(); w->ring.release(); w->table.release(); w->view.release(); w->taps.dev.release();
     delete w;
@@ -207,10 +199,7 @@ static int wb_step(csdr_wfbank *w, const csdr_wfbank_item *items, int n_items, i
     if (n_jobs == 0) { forget(); return CSDR_OK; }       // steps without points on slots without textures: nothing to quantise, nothing to keep
     const size_t lines_at = n_jobs * sizeof(WfbJob), bytes = lines_at + host_floats * sizeof(float);
     if (int rc = w->plan.begin(w->st, bytes)) { forget(); return rc; }
-    if (any_dev && from_boundary) {
-        CSDR_HIP_TRY(hipEventRecord(w->ev_in, w->ctx->stream));                  // the caller produced them on the boundary stream
-        CSDR_HIP_TRY(hipStreamWaitEvent(w->st, w->ev_in, 0));
-    }
+    if (any_dev && from_boundary) if (int rc = w->after_boundary()) return rc;  // the caller produced them on the boundary stream
     WfbJob *jobs = reinterpret_cast<WfbJob *>(w->plan.host());
     float *stage_h = reinterpret_cast<float *>(w->plan.host() + lines_at);
     const float *stage_d = reinterpret_cast<const float *>(w->plan.device() + lines_at);
@@ -432,7 +421,7 @@ extern "C" int csdr_wfbank_device_view(csdr_wfbank *w, const uint8_t **dev, int 
     DeviceScope dev__(w ? w->ctx : nullptr);
     if (!w || !dev) return fail(CSDR_EINVAL, "null argument");
     if (!w->ready || w->view_w == 0) return fail(CSDR_ESTATE, "nothing rendered yet (csdr_wfbank_render)");
-    if (int rc = wf_hand_over(w->ev_out, w->st, w->ctx->stream)) return rc;
+    if (int rc = w->hand_over()) return rc;
     *dev = reinterpret_cast<const uint8_t *>(w->view.p);
     if (pic_width) *pic_width = w->view_w;
     if (pic_height) *pic_height = w->view_h;

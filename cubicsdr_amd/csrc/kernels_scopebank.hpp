@@ -14,6 +14,7 @@
 // All LDS is dynamic (`smem`): scopebank_wave four floats; scopebank_spectrum 2 * L float2 (ping-pong of the transform) + 8 doubles of reduction scratch.
 #pragma once
 #include "common.hpp"
+#include "stream_order.hpp"
 #include "kernels_io.hpp"
 
 #if defined(CSDR_TU_SCOPEBANK)
@@ -30,7 +31,7 @@ struct ScopeBankJob {            // one non-empty process() input of a slot
     int32_t frame;               // output frame of the slot in this call
 };
 static_assert(sizeof(ScopeFrame) == 56 && sizeof(ScopeBankJob) == 64, "ScopeBankJob layout");
-struct ScopeBankRun { int32_t slot, job0, n_jobs, pad; };                // one workgroup of scopebank_spectrum: jobs [job0, job0 + n_jobs) of `slot`
+using ScopeBankRun = SlotRun;                                            // one workgroup of scopebank_spectrum: jobs [job0, job0 + n_jobs) of `slot`
 
 struct ScopeBankArgs {
     const ScopeBankRun *runs;

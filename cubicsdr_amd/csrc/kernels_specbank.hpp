@@ -17,6 +17,7 @@
 // share is their point loop: two fixed bins per point here, the view map and the hideDC gather there.
 #pragma once
 #include "common.hpp"
+#include "stream_order.hpp"
 #include "kernels_spec.hpp"
 
 #if defined(CSDR_TU_SPECBANK)
@@ -39,7 +40,7 @@ struct SpecBankJob {             // one non-empty process() input of a slot
     int32_t peak_reset_now;      // peakReset reached 0 in front of this input (:264-273)
 };
 static_assert(sizeof(SpecBankJob) == 32, "SpecBankJob layout");
-struct SpecBankRun { int32_t slot, job0, n_jobs, pad; };                 // one workgroup: jobs [job0, job0 + n_jobs) of `slot`
+using SpecBankRun = SlotRun;                                             // one workgroup: jobs [job0, job0 + n_jobs) of `slot`
 struct SpecBankTrk { double ceil_ma, ceil_maa, floor_ma, floor_maa, ceil_peak, floor_peak; };
 struct SpecBankFrame { double point_ceil, point_floor; int32_t hold, pad; };   // hold: the frame carries spectrum_hold_points
 

@@ -49,19 +49,16 @@ int sb_check_items(const Item *items, int n_items, int max_slots, bool *any_dev)
 }
 
 // The object both banks derive from.  Slot: SbSlot or a struct derived from it; Job: SpecBankJob or ViewBankJob (the fields the two share are
-// named alike).  All work runs on `st`, a stream of the object's own.
+// named alike).  All work runs on `st`, the side stream (ev_in: a producer's stream -> st for device inputs; ev_out: device_points); the slot order
+// of a call is SlotOrder's (stream_order.hpp).
 template <typename Slot, typename Job>
-struct SbBank {
-    csdr_ctx *ctx = nullptr;
-    hipStream_t st = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr;      // a producer's stream -> st (device inputs), st -> boundary stream (device_points)
+struct SbBank : SideStream, SlotOrder {
     bool ready = false;
     int F = 0, Fi = 0, max_slots = 0, max_frames = 0;
     float avg_rate = 0.65f, sf = 1.0f;                 // fft_average_rate (:36), scaleFactor
     float sf_last = 1.0f;                              // the scale factor the last call's frames were formed with (fft_ceiling = point_ceil / sf, :626)
     bool peak_hold = false;
     std::vector<Slot> slots;
-    std::vector<int> touched;                          // slots that got frames in the last call
     // ---- the per-slot frame store
     DevBuf<float2> tw4096, last, stage;                // (stage: the host inputs of a call)
     DevBuf<double> ma, maa, peak;
@@ -72,14 +69,10 @@ struct SbBank {
     // ---- a call's plan
     StageRing<kSbStage> plan;                          // SpecBankRun [runs] | Job [jobs] of the call being run
     std::vector<Slot> work;                            // copies the call is planned on
-    std::vector<int> n_jobs_of, job_at, cursor, run_slots;     // per slot: jobs of the call, its first job, the next one to fill; the slots that have jobs
     std::vector<Job> jobs_h;
 
     int create_base(csdr_ctx *c) {
-        ctx = c;
-        CSDR_HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-        CSDR_HIP_TRY(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
+        if (int rc = SideStream::create(c)) return rc;
         if (int rc = plan.create()) return rc;
         trk0.ceil_ma = trk0.ceil_maa = 100.0;           // ctor :32
         trk0.floor_ma = trk0.floor_maa = 0.0;           // ctor :33
@@ -87,9 +80,7 @@ struct SbBank {
         return CSDR_OK;
     }
     void destroy_base() {
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        if (ev_in) (void)hipEventDestroy(ev_in);
-        if (ev_out) (void)hipEventDestroy(ev_out);
+        SideStream::destroy();
         plan.destroy();
         tw4096.release(); last.release(); stage.release(); ma.release(); maa.release(); peak.release(); trk.release();
         points.release(); hold.release(); meta.release();
@@ -143,25 +134,12 @@ struct SbBank {
         if (!again) peak_hold = enabled != 0;
     }
 
-    // ---- the slot order of a call: a workgroup walks one slot's jobs, so the jobs lie slot by slot, each slot's in item order.
-    void count_begin() { n_jobs_of.assign((size_t)max_slots, 0); }
-    void count_job(int slot) { ++n_jobs_of[(size_t)slot]; }
-    // behind the count: where every slot's jobs lie, and the copies of the slots that run (a refused call leaves every slot as it was)
-    void order_jobs(size_t n_jobs) {
-        run_slots.clear();
-        job_at.assign((size_t)max_slots, 0);
+    // behind the count (SlotOrder): where every slot's jobs lie, and the copies of the slots that run (a refused call leaves every slot as it was)
+    void order_jobs() {
+        jobs_h.resize(order());
         work.resize((size_t)max_slots);
-        int at = 0;
-        for (int s = 0; s < max_slots; ++s)
-            if (n_jobs_of[(size_t)s]) {
-                run_slots.push_back(s); job_at[(size_t)s] = at; at += n_jobs_of[(size_t)s];
-                work[(size_t)s] = slots[(size_t)s];
-                work[(size_t)s].frames = 0;
-            }
-        jobs_h.resize(n_jobs);
-        cursor = job_at;
+        for (int s : run_slots) { work[(size_t)s] = slots[(size_t)s]; work[(size_t)s].frames = 0; }
     }
-    size_t next_job(int slot) { return (size_t)cursor[(size_t)slot]++; }      // the items are walked in order
 
     // the head of process() for one input: doPeak (:247) and the countdown (:264-273)
     void job_head(Job &jb, Slot &s) const {
@@ -191,9 +169,7 @@ struct SbBank {
     }
     // the planned call becomes the slots' state; from here on the call is enqueued
     void commit() {
-        for (int s : touched) slots[(size_t)s].frames = 0;
-        touched = run_slots;
-        for (int s : run_slots) slots[(size_t)s] = work[(size_t)s];
+        SlotOrder::commit([&](int s) { slots[(size_t)s].frames = 0; }, [&](int s) { slots[(size_t)s] = work[(size_t)s]; });
         sf_last = sf;
     }
 
@@ -204,7 +180,7 @@ struct SbBank {
         if (host_samples > stage.cap) CSDR_HIP_TRY(hipStreamSynchronize(st));        // (a kernel may still read the buffer being replaced)
         if (int rc = stage.reserve(host_samples)) return rc;
         size_t at = 0;
-        cursor = job_at;
+        rewind();
         for (int i = 0; i < n_items; ++i) {
             const Item &it = items[i];
             if (it.n == 0) continue;
@@ -219,18 +195,13 @@ struct SbBank {
     }
     // runs | jobs through the staging ring; begin() holds the one host wait of a call
     int upload_plan(const SpecBankRun **runs_d, const Job **jobs_d) {
-        const size_t n_runs = run_slots.size(), n_jobs = jobs_h.size();
-        const size_t bytes = n_runs * sizeof(SpecBankRun) + n_jobs * sizeof(Job);
+        const size_t n_jobs = jobs_h.size(), bytes = run_bytes() + n_jobs * sizeof(Job);
         if (int rc = plan.begin(st, bytes)) return rc;
-        SpecBankRun *runs_h = reinterpret_cast<SpecBankRun *>(plan.host());
-        for (size_t r = 0; r < n_runs; ++r) {
-            const int s = run_slots[r];
-            runs_h[r] = SpecBankRun{s, job_at[(size_t)s], n_jobs_of[(size_t)s], 0};
-        }
-        memcpy(plan.host() + n_runs * sizeof(SpecBankRun), jobs_h.data(), n_jobs * sizeof(Job));
+        fill_runs(plan.host());
+        memcpy(plan.host() + run_bytes(), jobs_h.data(), n_jobs * sizeof(Job));
         if (int rc = plan.uploaded(st, bytes)) return rc;
         *runs_d = reinterpret_cast<const SpecBankRun *>(plan.device());
-        *jobs_d = reinterpret_cast<const Job *>(plan.device() + n_runs * sizeof(SpecBankRun));
+        *jobs_d = reinterpret_cast<const Job *>(plan.device() + run_bytes());
         return CSDR_OK;
     }
     // the frame store's part of the kernel arguments (SpecBankArgs and ViewBankArgs name these fields alike)
@@ -297,8 +268,7 @@ template <typename Bank>
 int sb_device_points(Bank *b, int slot, const float **dev, int *frames) {
     if (int rc = sb_check_ready(b)) return rc;
     if (!dev || slot < 0 || slot >= b->max_slots) return fail(CSDR_EINVAL, "bad argument");
-    CSDR_HIP_TRY(hipEventRecord(b->ev_out, b->st));       // whatever the caller enqueues on the boundary stream next reads the finished points
-    CSDR_HIP_TRY(hipStreamWaitEvent(b->ctx->stream, b->ev_out, 0));
+    if (int rc = b->hand_over()) return rc;               // whatever the caller enqueues on the boundary stream next reads the finished points
     *dev = b->points.p + (size_t)slot * (size_t)b->max_frames * (size_t)b->F;
     if (frames) *frames = b->slots[(size_t)slot].frames;
     return CSDR_OK;

@@ -102,11 +102,4 @@ inline bool wf_good_line(const float *points, int n_floats_per_line, int fft_siz
     return points && (wf_line_is_pairs(n_floats_per_line, fft_size) || n_floats_per_line == fft_size);
 }
 
-// whatever the caller enqueues on the boundary stream next reads the picture finished on `st`
-inline int wf_hand_over(hipEvent_t ev_out, hipStream_t st, hipStream_t boundary) {
-    CSDR_HIP_TRY(hipEventRecord(ev_out, st));
-    CSDR_HIP_TRY(hipStreamWaitEvent(boundary, ev_out, 0));
-    return CSDR_OK;
-}
-
 }  // namespace csdr
