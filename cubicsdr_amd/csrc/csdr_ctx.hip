@@ -150,7 +150,8 @@ static const char *kKernelNames[KID_COUNT] = {
     "wfb_quantize", "wfb_update", "wfb_view_linear", "wfb_view_peak",
     "scopebank_wave", "scopebank_spectrum",
     "squelch_scan", "squelch_pack", "squelch_pcm16",
-    "viewbank_process"};
+    "viewbank_process",
+    "trace_lines", "trace_xy"};
 static int prof_drain(csdr_ctx *c) {
     if (int rc = c->sync_all()) return rc;
     std::lock_guard<std::mutex> lk(c->prof_mu);

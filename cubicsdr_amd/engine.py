@@ -906,6 +906,130 @@ class WaterfallBank:
             self.h = C.c_void_p()
 
 
+TRACE_KINDS = {"spectrum": H.TRACE_SPECTRUM, "y": H.TRACE_SCOPE_Y, "2y": H.TRACE_SCOPE_2Y, "xy": H.TRACE_SCOPE_XY}
+
+
+def _trace_kind(kind):
+    return TRACE_KINDS[kind] if isinstance(kind, str) else int(kind)
+
+
+def design_trace_envelope(points, width, height, kind="spectrum", hold=None, layout=0, n=None):
+    """the lit intervals of a polyline's columns in a width x height tile (host only; csdr_hip.h, "Trace bank", item 8) -> (lo, hi), int32 [2, width]:
+    row 0 the line (2Y: the upper sub-panel), row 1 the hold (2Y: the lower sub-panel), -1 where a column is unlit"""
+    a = np.ascontiguousarray(points, dtype=np.float32).ravel()
+    h = None if hold is None else np.ascontiguousarray(hold, dtype=np.float32).ravel()
+    n = a.size // (1 + int(layout)) if n is None else int(n)
+    lo, hi = (np.empty((2, max(int(width), 0)), np.int32) for _ in range(2))
+    H.check(H.lib().csdr_design_trace_envelope(a.ctypes.data_as(C.c_void_p) if a.size else None, None if h is None else h.ctypes.data_as(C.c_void_p), n,
+                                               int(layout), _trace_kind(kind), int(width), int(height), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p)))
+    return lo, hi
+
+
+class TraceBank:
+    """The spectrum, hold and scope lines of any number of items as tiles of one RGBA8 atlas with WaterfallBank.view's geometry (csdr_tracebank):
+    one launch for all line kinds, one for all XY items; points are read where they lie in HBM."""
+
+    def __init__(self, ctx, max_items=256, max_points=1 << 16):
+        self._l = H.lib()
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        H.check(self._l.csdr_tracebank_create(ctx.h, C.byref(self.h)))
+        self.setup(max_items, max_points)
+
+    def setup(self, max_items, max_points):
+        H.check(self._l.csdr_tracebank_setup(self.h, int(max_items), int(max_points)))
+        self.max_items, self.max_points = int(max_items), int(max_points)
+
+    def set_colors(self, bg=None, line=None, hold=None, axis_major=None, axis_minor=None):
+        """bg: 4 bytes RGBA; the others 3 bytes RGB; None leaves a colour as it is"""
+        arg = [None if c is None else (C.c_uint8 * k)(*[int(v) for v in c]) for c, k in ((bg, 4), (line, 3), (hold, 3), (axis_major, 3), (axis_minor, 3))]
+        H.check(self._l.csdr_tracebank_set_colors(self.h, *arg))
+
+    def try_render(self, items, width, height, atlas_cols=1, out=None, fetch=True):
+        """items: dicts with kind ("spectrum" | "y" | "2y" | "xy" or a CSDR_TRACE_* value), points and optionally hold (each a numpy float32 array,
+        a DevicePointer or None), layout (0 | 1), n (default: what the points hold); or None for an empty tile -> (return code, picture or None)"""
+        arr = (H.TraceItem * max(len(items), 1))()
+        keep = []
+
+        def place(p):
+            if p is None:
+                return None, 0, 0
+            if isinstance(p, DevicePointer):
+                keep.append(p)
+                return p.ptr, 1, p.n
+            a = np.ascontiguousarray(p, dtype=np.float32).ravel()
+            keep.append(a)
+            return (a.ctypes.data if a.size else None), 0, a.size
+        for k, it in enumerate(items):
+            if it is None:
+                continue
+            kind, layout = _trace_kind(it.get("kind", "spectrum")), int(it.get("layout", 0))
+            ptr, dev, floats = place(it.get("points"))
+            hptr, hdev, _ = place(it.get("hold"))
+            n = it.get("n")
+            if n is None:
+                n = floats if kind == H.TRACE_SCOPE_XY else floats // (1 + (layout & 1))
+            arr[k].points, arr[k].hold, arr[k].n, arr[k].layout, arr[k].kind = ptr, hptr, int(n), layout, kind
+            arr[k].is_dev = (H.TRACE_DEV_POINTS if dev else 0) | (H.TRACE_DEV_HOLD if hdev else 0)
+        n_items, cols = len(items), int(atlas_cols)
+        if not fetch:
+            return self._l.csdr_tracebank_render(self.h, arr, n_items, int(width), int(height), cols, None, 0), None
+        if out is None:
+            out = np.empty((max(-(-n_items // max(cols, 1)) * int(height), 0), max(cols * int(width), 0), 4), np.uint8)
+        rc = self._l.csdr_tracebank_render(self.h, arr, n_items, int(width), int(height), cols, out.ctypes.data_as(C.c_void_p), out.nbytes)
+        return rc, out
+
+    def render(self, items, width, height, atlas_cols=1, out=None, fetch=True):
+        """-> [tile rows * height, atlas_cols * width, 4] uint8; fetch=False renders it and leaves it on the device (device_view)"""
+        rc, pic = self.try_render(items, width, height, atlas_cols, out, fetch)
+        H.check(rc)
+        return pic
+
+    def render_spectra(self, bank, slots, width, height, frame=-1, hold=True, atlas_cols=1, fetch=True):
+        """frame `frame` (-1: the last one) of the listed slots of a SpectrumBank's or a ViewBank's last process, one tile per slot.  The points are
+        read where they lie in HBM (bank.device_points) and never cross the link.  The HOLD points come as a host item through bank.fetch_hold: no
+        existing call hands them out in HBM.  A slot without frames gives an empty tile."""
+        items = []
+        for s in slots:
+            p, frames = bank.device_points(s)
+            f = frames - 1 if frame < 0 else int(frame)
+            if frames <= 0 or f >= frames:
+                items.append(None)
+                continue
+            hp = bank.fetch_hold(s, f) if hold else None
+            items.append(dict(kind="spectrum", points=DevicePointer(p + 4 * f * bank.fft_size, bank.fft_size), n=bank.fft_size,
+                              hold=None if hp is None else hp[1::2].copy()))
+        return self.render(items, width, height, atlas_cols, fetch=fetch)
+
+    def render_scopes(self, scope_bank, slots, width, height, frame=-1, atlas_cols=1, fetch=True):
+        """the waveform item of frame `frame` (-1: the last one) of the listed slots of a ScopeBank's last process, one tile per slot, read where it
+        lies in HBM (scope_bank.device_points).  The kind comes from each frame's mode (Y, 2Y, XY); mode and length are only returned by
+        ScopeBank.fetch, so that call is made per slot for them.  A slot without a waveform gives an empty tile."""
+        items = []
+        for s in slots:
+            p, frames, stride = scope_bank.device_points(s, False)
+            f = frames - 1 if frame < 0 else int(frame)
+            it = scope_bank.fetch(s, f, False) if 0 <= f < frames else None
+            if it is None:
+                items.append(None)
+                continue
+            nf, kind = it["points"].size, H.TRACE_SCOPE_Y + int(it["mode"])
+            xy = kind == H.TRACE_SCOPE_XY
+            items.append(dict(kind=kind, points=DevicePointer(p + 4 * f * stride, nf), n=nf if xy else nf // 2, layout=0 if xy else 1))
+        return self.render(items, width, height, atlas_cols, fetch=fetch)
+
+    def device_view(self):
+        """(device pointer, width, height) of the last rendered picture in pixels; the context's boundary stream waits for it"""
+        p, w, h = C.c_void_p(), C.c_int(), C.c_int()
+        H.check(self._l.csdr_tracebank_device_view(self.h, C.byref(p), C.byref(w), C.byref(h)))
+        return p.value, w.value, h.value
+
+    def close(self):
+        if self.h:
+            self._l.csdr_tracebank_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class Distributor:
     """FFTDataDistributor's line cutting (csdr_distrib): the waterfall feed, cut where the block lies in HBM."""
 

@@ -99,6 +99,14 @@ class WfBankItem(C.Structure):
     _fields_ = [("slot", C.c_int32), ("n_floats_per_line", C.c_int32), ("points", C.c_void_p), ("is_dev", C.c_int32), ("n_lines", C.c_int32)]
 
 
+TRACE_SPECTRUM, TRACE_SCOPE_Y, TRACE_SCOPE_2Y, TRACE_SCOPE_XY = range(4)
+TRACE_DEV_POINTS, TRACE_DEV_HOLD = 1, 2
+
+
+class TraceItem(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("hold", C.c_void_p), ("n", C.c_int32), ("layout", C.c_int32), ("kind", C.c_int32), ("is_dev", C.c_int32)]
+
+
 class P2pOp(C.Structure):
     _fields_ = [("peer", C.c_int32), ("recv", C.c_int32), ("buf", C.c_void_p), ("n_samples", C.c_int64)]
 
@@ -371,6 +379,13 @@ ABI = {
     "csdr_wfbank_fetch_index": (_i, [_p, _i, _i, _p, _i64]),
     "csdr_wfbank_render": (_i, [_p, C.POINTER(_i), _i, _i, _i, _i, _i, _p, _i64]),
     "csdr_wfbank_device_view": (_i, [_p, _pp, C.POINTER(_i), C.POINTER(_i)]),
+    "csdr_tracebank_create": (_i, [_p, _pp]),
+    "csdr_tracebank_destroy": (None, [_p]),
+    "csdr_tracebank_setup": (_i, [_p, _i, _i]),
+    "csdr_tracebank_set_colors": (_i, [_p, _p, _p, _p, _p, _p]),
+    "csdr_tracebank_render": (_i, [_p, C.POINTER(TraceItem), _i, _i, _i, _i, _p, _i64]),
+    "csdr_tracebank_device_view": (_i, [_p, _pp, C.POINTER(_i), C.POINTER(_i)]),
+    "csdr_design_trace_envelope": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "csdr_table_run": (_i, [_p, C.POINTER(Constellation), _p, _i, C.POINTER(DigitalState), _p, _i, C.POINTER(_i), C.POINTER(_f)]),
 }
 

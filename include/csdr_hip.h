@@ -51,6 +51,7 @@ typedef struct csdr_wfbank csdr_wfbank;     /* N x WaterfallPanel, one per demod
 typedef struct csdr_scopebank csdr_scopebank; /* N x ScopeVisualProcessor, one per demodulator: every slot and frame of a call in two launches */
 typedef struct csdr_squelch csdr_squelch;     /* N x DemodulatorThread's level, floor, ceiling and squelch: every slot and block of an execute in one launch */
 typedef struct csdr_viewbank csdr_viewbank;   /* N x SpectrumVisualProcessor in zoomed view, one per demodulator: every slot and input of a call in one launch */
+typedef struct csdr_tracebank csdr_tracebank; /* the spectrum, hold and scope lines of any number of items as tiles of one RGBA8 atlas */
 
 /* ------------------------------------------------------------------ context */
 int         csdr_abi_version(void);
@@ -817,7 +818,8 @@ int  csdr_wfbank_device_view(csdr_wfbank *wb, const uint8_t **dev, int *pic_widt
  *    2 * max_samples for the waveform; *frames = 0 when that half was switched off.  The boundary stream is made to wait for them.  A spectrum frame
  *    with sample_rate == input_rate holds L floats = L/2 (x, y) pairs: the pair layout csdr_wfbank_step / csdr_waterfall_step take for
  *    fft_size = L/2 (n_floats_per_line = L), so an audio waterfall per demodulator needs no raster code of its own.
- * 9. Not in this object: a raster of the waveform trace; the tap of blocks other than the last one of an execute (the reference's one-deep queue
+ * 9. Not in this object: a raster of the waveform trace -- that is csdr_tracebank ("Trace bank" below), which reads the waveform items where
+ *    csdr_scopebank_device_points hands them out; the tap of blocks other than the last one of an execute (the reference's one-deep queue
  *    shows at most one per display refresh); L above 4096.
  * Ordering.  All work runs on a stream of the object's own, as the spectrum bank's does; the fetches synchronise it.  Host frames are copied into
  * page-locked staging inside the call, so the caller's buffers are free when it returns; device frames must have been produced on the boundary stream
@@ -1044,6 +1046,87 @@ int  csdr_viewbank_device_points(csdr_viewbank *vb, int slot, const float **dev,
 int  csdr_viewbank_slot_info(const csdr_viewbank *vb, int slot, csdr_viewbank_slot_state *out);
 /* the slot's fftLastData, 2 Fi floats (synchronises): the resampler's samples as the frame rule arranged them */
 int  csdr_viewbank_fetch_last(csdr_viewbank *vb, int slot, float *out, int cap_floats);
+
+/* ------------------------------------------------------------------ Trace bank: spectrum and scope lines as RGBA tiles
+ * The lines the reference draws above and beside the waterfall: the spectrum trace with its peak-hold trace (src/panel/SpectrumPanel.cpp:117-160)
+ * and the scope trace in its three modes (src/panel/ScopePanel.cpp:30-112).  A csdr_tracebank draws any number of polylines -- read where the
+ * spectrum, view and scope banks left them in HBM, or given on the host -- into ONE dense RGBA8 atlas with the tile geometry of csdr_wfbank_render,
+ * so the trace of list entry k lies over the waterfall tile of list entry k.  One launch draws every item of the line kinds, one every XY item,
+ * whatever the item count, and no point of the input is lost.  THE PICTURE IS THE LIBRARY'S OWN DEFINITION: GL_LINE_SMOOTH is implementation-defined
+ * and the reference has no pixel oracle, so, as with the waterfall's texel rounding, this block defines the picture and every implementation is held
+ * to it byte for byte.  After one float step per vertex everything is exact integer arithmetic (64-bit wherever a product could pass 2^31).
+ * 1. Quantiser.  A value y of a kind with constants (y0, s) -- (0, 1) for CSDR_TRACE_SPECTRUM, (-1, 0.5f) for the scope kinds -- in a panel of H rows:
+ *    u = (y - y0) * s, each operation rounded to float on its own; q = (int)floorf(u * (float)H) clamped to [0, H - 1]; u < 0 and -0.0 give 0, u >= 1
+ *    and +inf give H - 1, NaN gives 0.  The row is r = H - 1 - q, row 0 at the top.  The XY kind quantises x the same way into a column, with the tile
+ *    width in place of H and without the flip.
+ * 2. Columns.  A polyline has n >= 1 vertices; vertex i lies in column c_i = floor(i * W / n) of a tile W pixels wide -- the reference's
+ *    x = (float)i / (float)F (SpectrumVisualProcessor.cpp:542-576) and ((double)i / iMax - 0.5) * 2 (ScopeVisualProcessor.cpp:111).  The x of an
+ *    (x, y) pair is not read by the line kinds.  The trace ends in column c_{n-1}: short of the right edge when n < W, as the reference's.
+ * 3. Segments.  For vertices i, i + 1 with a = c_i, b = c_{i+1}, ra = r_i, rb = r_{i+1}: if a == b, column a receives the rows ra and rb.  Otherwise,
+ *    with d = b - a, every column c in [a, b] receives the two rows ra + rdiv((rb - ra) * t, 2 d) for t = clamp(2 (c - a) - 1, 0, 2 d) and
+ *    t = clamp(2 (c - a) + 1, 0, 2 d), where rdiv(p, q) = floor((2 p + q) / (2 q)) -- a floor division for negative p too.  A column's lit interval
+ *    [lo, hi] is the hull of everything it received (for n == 1 the single vertex); a column that received nothing is unlit.  So every column up to
+ *    c_{n-1} is lit, every vertex's row lies in its column's interval, and the intervals of adjacent columns share a row: the trace is connected and
+ *    loses no peak.  Rows [0, 9, 0] at W = 7 give lo = [0, 2, 7, 2, 0, -, -], hi = [2, 7, 9, 7, 2, -, -].
+ * 4. Kinds.  `n` counts vertices for the line kinds: layout 0 is n y values, layout 1 is n (x, y) pairs (what the fetches return and what the scope
+ *    bank's waveform items hold).
+ *    CSDR_TRACE_SPECTRUM (SpectrumPanel.cpp:149-160): one polyline of n vertices; if `hold` is not NULL, a second one of n vertices in the same
+ *      layout drawn over it: where the hold interval covers a pixel, out_c = (dst_c + hold_c + 1) >> 1 per colour channel (the reference's 0.5 alpha).
+ *      The dB grid and the frequency labels stay out.
+ *    CSDR_TRACE_SCOPE_Y (ScopePanel.cpp:32-44, :97-99): one polyline; under it the row of y = 0 in the minor axis colour.
+ *    CSDR_TRACE_SCOPE_2Y (:45-67, :100-105, constructor :7-16; height >= 2): an upper sub-panel of H / 2 rows and a lower one of H - H / 2.  The
+ *      first n / 2 vertices are drawn in the upper one, the next n / 2 in the lower one, each as a polyline of n / 2 vertices over the full width;
+ *      an odd last vertex is not drawn, and n == 1 draws the axes alone.  Each sub-panel is a panel of its own height with its own y = 0 row in the
+ *      minor colour; the first row of the lower sub-panel is in the major colour.
+ *    CSDR_TRACE_SCOPE_XY (:69-82, :88-89, :106-108): here n counts FLOATS, n / 2 points (x, y), whatever the layout says; a pixel hit k times is
+ *      min(255, bg_c + k * line_c) per channel (GL_ONE, GL_ONE).  The reference's 0.05-alpha background -- its persistence across frames -- stays out:
+ *      every render starts from the background.
+ * 5. Paint order per tile: background, minor axis rows, major axis row, line, hold.  Alpha is the background's alpha wherever a tile is drawn.
+ *    Colours are caller data, one set per object: bg RGBA; line, hold, axis_major, axis_minor RGB bytes; before any csdr_tracebank_set_colors:
+ *    black / 255, white, (0, 255, 0), white, (89, 89, 89).  A NULL argument of set_colors leaves that colour as it is.
+ * 6. Atlas: exactly csdr_wfbank_render's (item 6 of "Waterfall bank").  ceil(n_items / atlas_cols) * height rows by atlas_cols * width pixels; entry k
+ *    at tile row k / atlas_cols, tile column k % atlas_cols.  The tile of an item with n == 0 or points == NULL and the unused tiles of the last tile
+ *    row are all-zero bytes, rewritten on every call.  out_u8 == NULL leaves the picture on the device; csdr_tracebank_device_view returns the last
+ *    rendered picture and its size in pixels; it stays valid until the next render or setup.
+ * 7. Limits.  2 <= width <= 16384, 1 <= height <= 16384, 1 <= atlas_cols <= n_items <= max_items <= 2^20, 0 <= n <= max_points, 1 <= max_points
+ *    <= 2^21.  A kind or a layout out of range, bits of is_dev other than the two below, n < 0, 2Y at height 1, or device points that are not 4-byte
+ *    aligned: CSDR_EINVAL.  n above max_points, or a host buffer too small: CSDR_ERANGE.  A refusal renders nothing and changes nothing.
+ * 8. csdr_design_trace_envelope is items 1 - 4 on the host, no device needed: lo and hi hold 2 * width entries each -- [0, width) the line's intervals
+ *    (2Y: the upper sub-panel's), [width, 2 width) the hold's (2Y: the lower sub-panel's; nothing otherwise), in tile rows, lo = hi = -1 for an unlit
+ *    column.  CSDR_TRACE_SCOPE_XY has no envelope (CSDR_EINVAL); n == 0 leaves every column unlit; n above 2^21 is CSDR_ERANGE.
+ * Ordering is the waterfall bank's.  All work runs on a stream of the object's own; a render into host memory synchronises it.  Host points are
+ * copied into page-locked staging inside the call, so the caller's buffers are free when it returns.  Device points must have been produced on, or
+ * handed to, the boundary stream -- what csdr_specbank_device_points, csdr_viewbank_device_points and csdr_scopebank_device_points do -- are ordered
+ * behind it by an event and stay unchanged until the next synchronising call on this object.  csdr_tracebank_device_view makes the boundary stream
+ * wait for the picture.  The producing banks are not touched and wait for nobody here: a caller who keeps the picture on the device (out_u8 == NULL)
+ * synchronises this object -- a render into host memory, or csdr_tracebank_device_view and a synchronise of the boundary stream -- before the
+ * producer's next process, the rule those device_points calls give every reader.  A call waits on the host only for the upload of its records that
+ * last used the same page-locked staging set, two calls ago. */
+#define CSDR_TRACE_SPECTRUM  0
+#define CSDR_TRACE_SCOPE_Y   1
+#define CSDR_TRACE_SCOPE_2Y  2
+#define CSDR_TRACE_SCOPE_XY  3
+#define CSDR_TRACE_DEV_POINTS 1  /* bits of csdr_trace_item.is_dev: `points` is device memory */
+#define CSDR_TRACE_DEV_HOLD   2  /* `hold` is device memory */
+typedef struct csdr_trace_item {
+    const float *points;       /* the polyline (XY: the points); NULL: an empty tile */
+    const float *hold;         /* CSDR_TRACE_SPECTRUM: the hold points, n vertices in the same layout, or NULL; not read by the other kinds */
+    int32_t n;                 /* vertices (XY: floats); 0: an empty tile */
+    int32_t layout;            /* 0: y values; 1: (x, y) pairs */
+    int32_t kind;              /* CSDR_TRACE_* */
+    int32_t is_dev;            /* CSDR_TRACE_DEV_* bits; device memory is 4-byte aligned */
+} csdr_trace_item;
+CSDR_STATIC_ASSERT(sizeof(csdr_trace_item) == 32 && offsetof(csdr_trace_item, hold) == 8 && offsetof(csdr_trace_item, n) == 16 &&
+                   offsetof(csdr_trace_item, is_dev) == 28, "csdr_trace_item layout");
+int  csdr_tracebank_create(csdr_ctx *ctx, csdr_tracebank **out);
+void csdr_tracebank_destroy(csdr_tracebank *tb);
+int  csdr_tracebank_setup(csdr_tracebank *tb, int max_items, int max_points);
+int  csdr_tracebank_set_colors(csdr_tracebank *tb, const uint8_t *bg /*[4]*/, const uint8_t *line /*[3]*/, const uint8_t *hold /*[3]*/,
+                               const uint8_t *axis_major /*[3]*/, const uint8_t *axis_minor /*[3]*/);
+int  csdr_tracebank_render(csdr_tracebank *tb, const csdr_trace_item *items, int n_items, int width, int height, int atlas_cols, uint8_t *out_u8, int64_t cap);
+int  csdr_tracebank_device_view(csdr_tracebank *tb, const uint8_t **dev, int *pic_width, int *pic_height);
+int  csdr_design_trace_envelope(const float *points, const float *hold_or_null, int n, int layout, int kind, int width, int height,
+                                int32_t *lo /*[2 width]*/, int32_t *hi /*[2 width]*/);
 
 /* ------------------------------------------------------------------ ingest
  * The reference's reader fills pooled SDRThreadIQData blocks (SoapySDRThread.cpp:221-225) and SDRPostThread hands ONE buffer to the
