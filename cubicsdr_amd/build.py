@@ -6,7 +6,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # one translation unit per object of include/csdr_hip.h (an edit rebuilds its own unit; the units compile in parallel)
-UNITS = ["csdr_ctx", "csdr_post", "csdr_bank", "csdr_spec", "csdr_io", "csdr_comm", "csdr_digital", "csdr_waterfall", "csdr_distrib", "csdr_specbank", "csdr_wfbank", "csdr_scopebank", "csdr_squelch", "csdr_viewbank", "csdr_tracebank"]
+UNITS = ["csdr_ctx", "csdr_post", "csdr_bank", "csdr_spec", "csdr_io", "csdr_comm", "csdr_digital", "csdr_waterfall", "csdr_distrib", "csdr_specbank", "csdr_wfbank", "csdr_scopebank", "csdr_squelch", "csdr_viewbank", "csdr_tracebank", "csdr_overlay"]
 SRCS = [os.path.join(HERE, "csrc", u + ".hip") for u in UNITS]
 OBJ_DIR = os.path.join(HERE, "csrc", "_obj")
 OUT = os.path.join(HERE, "libcsdr_hip.so")
@@ -25,7 +25,8 @@ DESIGN_OUT = os.path.join(HERE, "libcsdr_design.so")
 
 def build_design(force=False, verbose=True):
     """host-only helper library (g++): the cold-path filter design, testable without a GPU"""
-    deps = [DESIGN_SRC, os.path.join(HERE, "csrc", "design.hpp")]
+    deps = [DESIGN_SRC, os.path.join(HERE, "csrc", "design.hpp"), os.path.join(HERE, "csrc", "design_overlay_capi.hpp"),
+            os.path.join(os.path.dirname(HERE), "include", "csdr_hip.h")]
     if not force and os.path.exists(DESIGN_OUT) and all(os.path.getmtime(d) <= os.path.getmtime(DESIGN_OUT) for d in deps):
         return DESIGN_OUT
     cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", DESIGN_SRC, "-o", DESIGN_OUT]

@@ -15,7 +15,7 @@
 // every kernel has internal linkage: the kernel headers are included by several translation units (for the object layouts and constants next to
 // the kernels).  A kernel has ONE home unit, the one that launches it: csdr_post.hip (CSDR_TU_POST: channelizers, DC blocker), csdr_bank.hip
 // (CSDR_TU_BANK: front-ends, modems, audio), csdr_spec.hip (CSDR_TU_SPEC: the spectrum chain), csdr_io.hip (scope, mixer, ingest), csdr_waterfall.hip
-// (the raster; its switch sits in kernels_waterfall.hpp), csdr_distrib.hip (the waterfall feed; kernels_distrib.hpp), csdr_specbank.hip (the spectrum bank; kernels_specbank.hpp), csdr_scopebank.hip (the scope bank; kernels_scopebank.hpp), csdr_squelch.hip (the squelch bank; kernels_squelch.hpp), csdr_viewbank.hip (the view bank; kernels_viewbank.hpp), csdr_tracebank.hip (the trace bank; kernels_tracebank.hpp).  Elsewhere a
+// (the raster; its switch sits in kernels_waterfall.hpp), csdr_distrib.hip (the waterfall feed; kernels_distrib.hpp), csdr_specbank.hip (the spectrum bank; kernels_specbank.hpp), csdr_scopebank.hip (the scope bank; kernels_scopebank.hpp), csdr_squelch.hip (the squelch bank; kernels_squelch.hpp), csdr_viewbank.hip (the view bank; kernels_viewbank.hpp), csdr_tracebank.hip (the trace bank; kernels_tracebank.hpp), csdr_overlay.hip (the overlay bank; kernels_overlay.hpp).  Elsewhere a
 // kernel that is not a template already is declared as one that is never instantiated: parsed, not compiled (round 4 built chan_analyze_fft and the
 // demodulator kernels three times and the spectrum chain twice).
 #define CSDR_KERNEL static __global__
@@ -333,6 +333,7 @@ enum CsdrKernelId {
     KID_SQUELCH_SCAN, KID_SQUELCH_PACK, KID_SQUELCH_PCM16,
     KID_VIEWBANK,
     KID_TRACE_LINES, KID_TRACE_XY,
+    KID_OVERLAY_COMPOSE,
     KID_COUNT
 };
 

@@ -151,7 +151,8 @@ static const char *kKernelNames[KID_COUNT] = {
     "scopebank_wave", "scopebank_spectrum",
     "squelch_scan", "squelch_pack", "squelch_pcm16",
     "viewbank_process",
-    "trace_lines", "trace_xy"};
+    "trace_lines", "trace_xy",
+    "overlay_compose"};
 static int prof_drain(csdr_ctx *c) {
     if (int rc = c->sync_all()) return rc;
     std::lock_guard<std::mutex> lk(c->prof_mu);

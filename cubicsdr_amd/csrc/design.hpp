@@ -15,6 +15,8 @@
 #include <complex>
 #include <vector>
 
+#include "../../include/csdr_hip.h"
+
 namespace csdr {
 namespace design {
 
@@ -737,6 +739,161 @@ inline int optimal_element_count(int64_t sample_rate, int fps, int num_channels)
     int n = (int)std::floor((double)sample_rate / (double)fps);
     n = (int)(std::ceil((double)n / (double)num_channels) * num_channels);
     return n;
+}
+
+// ---- overlay planners: the reference's display arithmetic as records and csdr_overlay_prims (include/csdr_hip.h, "Overlay bank", a - e) -------
+// NDC -> pixels, one rule for every planner, in double
+inline int ndc_hb(double u, int W) { const double b = std::floor((u + 1.0) * 0.5 * (double)W); return b < 0.0 ? 0 : (b > (double)W ? W : (int)b); }
+inline int ndc_vb(double v, int H) { const double b = std::floor((1.0 - v) * 0.5 * (double)H); return b < 0.0 ? 0 : (b > (double)H ? H : (int)b); }
+inline uint8_t unit_byte(double c) { return (uint8_t)(int)(c * 255.0 + 0.5); }
+inline bool view_ok(int w, int h) { return w >= 1 && w <= 16384 && h >= 1 && h <= 16384; }
+
+// SpectrumPanel.cpp:171-277, with the reference's types: long long frequencies, long double steps, double m, float view sizes
+inline int freq_scale(int64_t freq, int64_t bandwidth, int view_w, int view_h, double font_scale, csdr_freq_scale *out, csdr_freq_tick *ticks, int cap) {
+    if (!out || (cap > 0 && !ticks) || cap < 0 || bandwidth < 1 || !view_ok(view_w, view_h) || !(font_scale > 0.0)) return CSDR_EINVAL;
+    const float viewWidth = (float)view_w, viewHeight = (float)view_h;
+    const long long leftFreq = (long long)((double)freq - ((double)bandwidth / 2.0));                 // :171
+    const long long rightFreq = (long long)((double)leftFreq + (double)bandwidth);                    // :172
+    if (rightFreq - leftFreq < 1) return CSDR_EINVAL;
+    const long double span = (long double)(rightFreq - leftFreq);
+    const long long hzStep = 1000000;
+    long double mhzStep = (100000.0 / span) * 2.0;                                                   // :176
+    double mhzVisualStep = 0.1;
+    int precision = 1;
+    auto narrow = [&]() { return mhzStep * 0.5 * viewWidth < 40 * font_scale; };
+    if (narrow()) {                                                                                  // :184-216
+        static const double ladder[7] = {0.25, 0.5, 1.0, 2.5, 5.0, 10.0, 50.0};
+        for (int k = 0; k < 7 && (k == 0 || narrow()); ++k) { mhzStep = ((ladder[k] * 1000000.0) / span) * 2.0; mhzVisualStep = ladder[k]; }
+    } else if (mhzStep * 0.5 * viewWidth > 350 * font_scale) {                                       // :217-221
+        mhzStep = (10000.0 / span) * 2.0;
+        mhzVisualStep = 0.01;
+        precision = 2;
+    }
+    const long long firstMhz = (leftFreq / hzStep) * hzStep;                                         // :223, truncating
+    const long double mhzStart = ((long double)(firstMhz - leftFreq) / span) * 2.0;
+    long double currentMhz = truncl(floorl(firstMhz / (long double)1000000.0));
+    out->step_mhz = mhzVisualStep; out->precision = precision; out->pad = 0;
+    out->tick_top = 1.0 - (5.0 / viewHeight);                                                        // :229
+    out->label_y = 1.0 - (16.0 / viewHeight) * font_scale; out->font_size = 12;                      // :228
+    if (viewHeight > 135) { out->font_size = 16; out->label_y = 1.0 - (18.0 / viewHeight) * font_scale; }
+    out->tick_rows = ndc_vb(out->tick_top, view_h); out->label_row = ndc_vb(out->label_y, view_h);
+    int n = 0;
+    long long turns = 0;
+    for (double m = (double)(-1.0 + mhzStart), mMax = (double)(1.0 + ((mhzStart > 0) ? mhzStart : -mhzStart)); m <= mMax; m = (double)(m + mhzStep)) {    // :241
+        if (++turns > (1 << 20)) return CSDR_EINVAL;
+        if (m < -1.0) { currentMhz += mhzVisualStep; continue; }
+        if (m > 1.0) break;
+        if (n < cap) {
+            csdr_freq_tick &t = ticks[n];
+            double intpart;
+            t.m = m; t.value = (double)currentMhz;
+            t.major = std::modf((double)currentMhz, &intpart) < 0.001 ? 1 : 0;                       // :253-255
+            t.column = ndc_hb(m, view_w);
+            std::snprintf(t.label, sizeof t.label, "%.*Lf", precision, currentMhz);                  // :249
+        }
+        ++n;
+        currentMhz += mhzVisualStep;
+    }
+    out->n_ticks = n;
+    return n > cap ? CSDR_ERANGE : CSDR_OK;
+}
+
+// SpectrumPanel.cpp:117-147
+inline int db_grid(float floor_value, float ceil_value, csdr_db_grid_range *ranges, int *n_ranges, double *p_out, int cap) {
+    if (!ranges || !n_ranges || (cap > 0 && !p_out) || cap < 0 || !std::isfinite(floor_value) || !std::isfinite(ceil_value)) return CSDR_EINVAL;
+    const double range = ceil_value - floor_value;                                                   // :119, a float difference
+    static const double table[3][4] = {{90.0, 5000.0, 10.0, 100.0}, {20.0, 150.0, 10.0, 10.0}, {-20.0, 30.0, 10.0, 1.0}};
+    int nr = 0, np = 0;
+    for (const auto &i : table) {
+        const double rangeMin = i[0], rangeMax = i[1], rangeTrans = i[2], rangeStep = i[3];
+        if (!(range >= rangeMin && range <= rangeMax)) continue;
+        double a = 1.0, p = 0;
+        if (range <= rangeMin + rangeTrans) a *= (range - rangeMin) / rangeTrans;
+        if (range >= rangeMax - rangeTrans) a *= (rangeTrans - (range - (rangeMax - rangeTrans))) / rangeTrans;
+        csdr_db_grid_range &r = ranges[nr++];
+        r.alpha = a; r.step = rangeStep; r.first = np; r.count = 0;
+        for (double l = floor_value; l <= ceil_value + rangeStep; l += rangeStep) {                  // :141
+            p += rangeStep / range;
+            if (np < cap) p_out[np] = p;
+            ++np; ++r.count;
+        }
+    }
+    *n_ranges = nr;
+    return np > cap ? CSDR_ERANGE : CSDR_OK;
+}
+
+// SpectrumPanel.cpp:281-303
+inline int db_labels(float floor_value, float ceil_value, int fft_size, double db_offset, char *ceil_label, char *floor_label, int cap) {
+    if (!ceil_label || !floor_label || cap < 1) return CSDR_EINVAL;
+    ceil_label[0] = floor_label[0] = 0;
+    if (ceil_value == floor_value || fft_size == 0) return CSDR_OK;
+    const int a = std::snprintf(ceil_label, (size_t)cap, "%.1fdB", db_offset + 20.0 * std::log10(2.0 * (ceil_value) / (double)fft_size));
+    const int b = std::snprintf(floor_label, (size_t)cap, "%.1fdB", db_offset + 20.0 * std::log10(2.0 * (floor_value) / (double)fft_size));
+    return a >= cap || b >= cap ? CSDR_ERANGE : CSDR_OK;
+}
+
+// PrimaryGLContext.cpp:89-164, :168-197, in float as the reference
+inline int demod_marker(int64_t demod_freq, int bandwidth, int sideband, int64_t center_freq, int64_t srate, int flags, int view_w, int view_h,
+                        const uint8_t *rgb, csdr_demod_marker *out, csdr_overlay_prim *prims, int *n_prims) {
+    if (!rgb || !out || !prims || !n_prims || srate < 1 || !view_ok(view_w, view_h) || sideband < CSDR_SIDEBAND_BOTH || sideband > CSDR_SIDEBAND_LSB) return CSDR_EINVAL;
+    const float viewHeight = (float)view_h, viewWidth = (float)view_w;
+    float uxPos = (float)(demod_freq - (center_freq - srate / 2)) / (float)srate;                    // :89
+    uxPos = (float)((uxPos - 0.5) * 2.0);
+    const float ofs = ((float)bandwidth) / (float)srate;                                             // :98
+    const float ofsLeft = sideband != CSDR_SIDEBAND_USB ? ofs : 0, ofsRight = sideband != CSDR_SIDEBAND_LSB ? ofs : 0;
+    const float labelHeight = (float)(20.0 / viewHeight);
+    const float hPos = (float)(-1.0 + labelHeight);
+    const int x0 = ndc_hb(uxPos - ofsLeft, view_w), x1 = ndc_hb(uxPos + ofsRight, view_w), ytop = ndc_vb(hPos + labelHeight, view_h);
+    int n = 0;
+    auto rect = [&](int x, int y, int w, int h, uint8_t r, uint8_t g, uint8_t b, double alpha, int mode) {
+        prims[n++] = csdr_overlay_prim{x, y, w < 0 ? 0 : w, h < 0 ? 0 : h, {r, g, b, unit_byte(alpha)}, mode, -1, 0};
+    };
+    rect(x0, ytop, x1 - x0, view_h - ytop, 0, 0, 0, 0.35f, CSDR_OVL_OVER);                           // :110-134
+    rect(x0, 0, x1 - x0, view_h, rgb[0], rgb[1], rgb[2], 0.2f, CSDR_OVL_ADD);                        // :136-145
+    out->narrow = ofs * 2.0 < 16.0 / viewWidth ? 1 : 0;                                              // :147
+    if (out->narrow) rect(x0, ytop, x1 - x0, view_h - ytop, rgb[0], rgb[1], rgb[2], 0.2f, CSDR_OVL_ADD);
+    const int xc = ndc_hb(uxPos, view_w);
+    if ((flags & CSDR_MARKER_CENTERLINE) && xc < view_w) rect(xc, 0, 1, view_h, rgb[0], rgb[1], rgb[2], 0.5, CSDR_OVL_ADD);      // :158-164
+    *n_prims = n;
+    out->ux = uxPos; out->ofs_left = ofsLeft; out->ofs_right = ofsRight; out->label_v = hPos;
+    out->halign = sideband == CSDR_SIDEBAND_USB ? CSDR_ALIGN_LEFT : (sideband == CSDR_SIDEBAND_LSB ? CSDR_ALIGN_RIGHT : CSDR_ALIGN_CENTER);   // :191-197
+    out->label_x = xc; out->label_y = ndc_vb(hPos, view_h);
+    char letters[4];
+    int nl = 0;
+    if (flags & CSDR_MARKER_DELTA_LOCK) letters[nl++] = 'V';                                         // :170-182
+    if (flags & CSDR_MARKER_RECORDING) letters[nl++] = 'R';
+    if (flags & CSDR_MARKER_MUTED) letters[nl++] = 'M'; else if (flags & CSDR_MARKER_SOLO) letters[nl++] = 'S';
+    letters[nl] = 0;
+    std::snprintf(out->prefix, sizeof out->prefix, nl ? "[%s] " : "%s", letters);
+    return CSDR_OK;
+}
+
+// one string as masked primitives (csdr_hip.h, "Overlay bank", e)
+inline int text_prims(const csdr_glyph *glyphs, int n_glyphs, int line_height, const char *str, int x, int y, int halign, int valign, const uint8_t *rgba, int mode,
+                      csdr_overlay_prim *out, int cap, int *n_out) {
+    if (!str || !rgba || !n_out || n_glyphs < 0 || (n_glyphs > 0 && !glyphs) || (cap > 0 && !out) || cap < 0 || line_height < 0 || halign < CSDR_ALIGN_LEFT ||
+        halign > CSDR_ALIGN_RIGHT || valign < CSDR_ALIGN_TOP || valign > CSDR_ALIGN_BOTTOM || mode < CSDR_OVL_OVER || mode > CSDR_OVL_COPY) return CSDR_EINVAL;
+    auto find = [&](char c) -> const csdr_glyph * {
+        for (int k = 0; k < n_glyphs; ++k) if (glyphs[k].id == (int)(unsigned char)c) return &glyphs[k];
+        return nullptr;
+    };
+    auto floor_half = [](long long v) { return (v - (v < 0 ? 1 : 0)) / 2; };
+    long long width = 0;
+    for (const char *c = str; *c; ++c) if (const csdr_glyph *g = find(*c)) { if (g->w < 0 || g->h < 0) return CSDR_EINVAL; width += g->xadvance; }
+    long long pen = halign == CSDR_ALIGN_LEFT ? x : (halign == CSDR_ALIGN_CENTER ? x - floor_half(width) : x - width);
+    const long long top = valign == CSDR_ALIGN_TOP ? y : (valign == CSDR_ALIGN_CENTER ? y - floor_half(line_height) : (long long)y - line_height);
+    int n = 0;
+    for (const char *c = str; *c; ++c) {
+        const csdr_glyph *g = find(*c);
+        if (!g) continue;
+        if (g->w > 0 && g->h > 0) {
+            if (n < cap) out[n] = csdr_overlay_prim{(int32_t)(pen + g->xoffset), (int32_t)(top + g->yoffset), g->w, g->h, {rgba[0], rgba[1], rgba[2], rgba[3]}, mode, g->x, g->y};
+            ++n;
+        }
+        pen += g->xadvance;
+    }
+    *n_out = n;
+    return n > cap ? CSDR_ERANGE : CSDR_OK;
 }
 
 }  // namespace design

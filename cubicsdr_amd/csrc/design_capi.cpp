@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "design.hpp"
+#include "design_overlay_capi.hpp"  // csdr_design_freq_scale, _db_grid, _db_labels, _demod_marker, _text
 
 using namespace csdr::design;
 

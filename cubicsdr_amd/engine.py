@@ -1030,6 +1030,214 @@ class TraceBank:
             self.h = C.c_void_p()
 
 
+PRIM_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("rgba", "u1", (4,)), ("mode", "<i4"), ("mask_x", "<i4"), ("mask_y", "<i4")])
+GLYPH_DTYPE = np.dtype([(k, "<i4") for k in ("id", "x", "y", "w", "h", "xoffset", "yoffset", "xadvance")])
+OVL_MODES = {"over": H.OVL_OVER, "add": H.OVL_ADD, "copy": H.OVL_COPY}
+_ALIGN_H = {"left": H.ALIGN_LEFT, "center": H.ALIGN_CENTER, "right": H.ALIGN_RIGHT}
+_ALIGN_V = {"top": H.ALIGN_TOP, "center": H.ALIGN_CENTER, "bottom": H.ALIGN_BOTTOM}
+_SIDEBANDS = {"both": H.SIDEBAND_BOTH, "usb": H.SIDEBAND_USB, "lsb": H.SIDEBAND_LSB}
+
+
+def _named(table, v):
+    return table[v] if isinstance(v, str) else int(v)
+
+
+def overlay_prims(records=()):
+    """csdr_overlay_prim records as one numpy array (PRIM_DTYPE): from (x, y, w, h, rgba, mode[, mask_x, mask_y]) tuples, or arrays to concatenate"""
+    parts = []
+    for r in records:
+        if isinstance(r, np.ndarray):
+            parts.append(r.astype(PRIM_DTYPE, copy=False).ravel())
+            continue
+        a = np.zeros(1, PRIM_DTYPE)
+        a[0] = (r[0], r[1], r[2], r[3], tuple(r[4]), _named(OVL_MODES, r[5]), r[6] if len(r) > 6 else -1, r[7] if len(r) > 7 else 0)
+        parts.append(a)
+    return np.concatenate(parts) if parts else np.zeros(0, PRIM_DTYPE)
+
+
+def _glyph_table(glyphs):
+    g = np.ascontiguousarray(glyphs, dtype=GLYPH_DTYPE).ravel()
+    return g, g.ctypes.data_as(C.POINTER(H.Glyph))
+
+
+def design_freq_scale(freq, bandwidth, view_w, view_h, font_scale=1.0):
+    """SpectrumPanel's frequency scale (host only; csdr_hip.h, "Overlay bank", a) -> dict(step_mhz, precision, tick_top, label_y, font_size,
+    tick_rows, label_row, ticks=[dict(m, value, label, major, column)])"""
+    sc, cap = H.FreqScale(), 64
+    while True:
+        ticks = (H.FreqTick * cap)()
+        rc = H.lib().csdr_design_freq_scale(int(freq), int(bandwidth), int(view_w), int(view_h), float(font_scale), C.byref(sc), ticks, cap)
+        if rc != -5:
+            break
+        cap = sc.n_ticks
+    H.check(rc)
+    out = {k: getattr(sc, k) for k in ("step_mhz", "precision", "tick_top", "label_y", "font_size", "tick_rows", "label_row")}
+    out["ticks"] = [dict(m=t.m, value=t.value, label=t.label.decode(), major=bool(t.major), column=t.column) for t in ticks[:sc.n_ticks]]
+    return out
+
+
+def design_db_grid(floor, ceil):
+    """SpectrumPanel's dB grid (host only; "Overlay bank", b) -> [dict(alpha, step, p=float64 array)] for each range that applies, in order"""
+    ranges, n, p = (H.DbGridRange * 3)(), C.c_int(), (C.c_double * 256)()
+    H.check(H.lib().csdr_design_db_grid(float(floor), float(ceil), ranges, C.byref(n), p, 256))
+    return [dict(alpha=r.alpha, step=r.step, p=np.array(p[r.first:r.first + r.count], np.float64)) for r in ranges[:n.value]]
+
+
+def design_db_labels(floor, ceil, fft_size, db_offset=0.0):
+    """SpectrumPanel's two dB labels (host only; "Overlay bank", c) -> (ceil label, floor label)"""
+    a, b = C.create_string_buffer(64), C.create_string_buffer(64)
+    H.check(H.lib().csdr_design_db_labels(float(floor), float(ceil), int(fft_size), float(db_offset), a, b, 64))
+    return a.value.decode(), b.value.decode()
+
+
+def design_demod_marker(demod_freq, bandwidth, sideband, center_freq, srate, flags, view_w, view_h, rgb=(255, 255, 255)):
+    """DrawDemodInfo's marker (host only; "Overlay bank", d) -> dict(ux, ofs_left, ofs_right, label_v, narrow, halign, label_x, label_y, prefix, prims)"""
+    m, prims, n = H.DemodMarker(), np.zeros(4, PRIM_DTYPE), C.c_int()
+    H.check(H.lib().csdr_design_demod_marker(int(demod_freq), int(bandwidth), _named(_SIDEBANDS, sideband), int(center_freq), int(srate), int(flags), int(view_w),
+                                             int(view_h), (C.c_uint8 * 3)(*[int(v) for v in rgb]), C.byref(m), prims.ctypes.data_as(C.POINTER(H.OverlayPrim)), C.byref(n)))
+    out = {k: getattr(m, k) for k in ("ux", "ofs_left", "ofs_right", "label_v", "narrow", "halign", "label_x", "label_y")}
+    out["narrow"], out["prefix"], out["prims"] = bool(m.narrow), m.prefix.decode(), prims[:n.value].copy()
+    return out
+
+
+def design_text(glyphs, line_height, text, x, y, halign="left", valign="top", rgba=(255, 255, 255, 255), mode="over"):
+    """one string as masked primitives (host only; "Overlay bank", e) -> PRIM_DTYPE array.  glyphs: GLYPH_DTYPE records (parse_bmfont)"""
+    g, gp = _glyph_table(glyphs)
+    raw = text.encode("latin-1", "replace") if isinstance(text, str) else bytes(text)
+    out, n = np.zeros(max(len(raw), 1), PRIM_DTYPE), C.c_int()
+    H.check(H.lib().csdr_design_text(gp, g.size, int(line_height), raw, int(x), int(y), _named(_ALIGN_H, halign), _named(_ALIGN_V, valign),
+                                     (C.c_uint8 * 4)(*[int(v) for v in rgba]), _named(OVL_MODES, mode), out.ctypes.data_as(C.POINTER(H.OverlayPrim)), out.size, C.byref(n)))
+    return out[:n.value].copy()
+
+
+def parse_bmfont(text):
+    """the text form of an AngelCode .fnt -> dict(glyphs=GLYPH_DTYPE array, line_height, base, scale_w, scale_h, pages={id: file}).  The page images
+    are not decoded: the coverage plane OverlayBank.set_font takes is the caller's to produce from them."""
+    import shlex
+    glyphs, info = [], dict(line_height=0, base=0, scale_w=0, scale_h=0, pages={})
+    for ln in text.splitlines():
+        words = shlex.split(ln)
+        if not words:
+            continue
+        kv = dict(w.split("=", 1) for w in words[1:] if "=" in w)
+        if words[0] == "common":
+            info.update(line_height=int(kv.get("lineHeight", 0)), base=int(kv.get("base", 0)), scale_w=int(kv.get("scaleW", 0)), scale_h=int(kv.get("scaleH", 0)))
+        elif words[0] == "page":
+            info["pages"][int(kv.get("id", 0))] = kv.get("file", "")
+        elif words[0] == "char":
+            glyphs.append(tuple(int(kv.get(k, 0)) for k in ("id", "x", "y", "width", "height", "xoffset", "yoffset", "xadvance")))
+    info["glyphs"] = np.array(glyphs, GLYPH_DTYPE) if glyphs else np.zeros(0, GLYPH_DTYPE)
+    return info
+
+
+def spectrum_annotations(width, height, freq, bandwidth, floor, ceil, fft_size, glyphs, line_height, markers=(), db_offset=0.0, font_scale=1.0,
+                         freq_line=(255, 255, 255), text=(255, 255, 255)):
+    """One tile's primitive list (PRIM_DTYPE) in the order grid, ticks, MHz labels, dB labels, markers, for a tile that shows `bandwidth` Hz around
+    `freq` between the levels floor and ceil: csdr_hip.h, "Overlay bank", a - e, put together.  The grid rows are CSDR_OVL_ADD in 0.12 grey; a tick
+    fills rows [0, tick_rows) in freq_line (4 columns, major) or 0.65 of it (1 column); a MHz label is centred on (column, label_row) in `text`; the
+    ceil label is right-aligned at column min(88 font_scale, width) against the top edge, the floor label against the bottom edge (the reference's
+    two 88 x 14 panels, SpectrumPanel.cpp:282-302, without their grounds).  markers: dicts with freq, bandwidth, and optionally sideband, flags,
+    rgb, label; each gives design_demod_marker's primitives and its label in white at alpha 0.8."""
+    W, Hh = int(width), int(height)
+    out = []
+    for rng in design_db_grid(floor, ceil):
+        a = int(rng["alpha"] * 255 + 0.5)
+        for p in rng["p"]:
+            if 0.0 <= p <= 1.0:
+                row = int(min(max(np.floor((1.0 - (2.0 * p - 1.0)) * 0.5 * Hh), 0), Hh))
+                if row < Hh:
+                    out.append((0, row, W, 1, (31, 31, 31, a), H.OVL_ADD))
+    sc = design_freq_scale(freq, bandwidth, W, Hh, font_scale)
+    minor = tuple(int(c * 0.65 + 0.5) for c in freq_line)
+    for t in sc["ticks"]:
+        k = 4 if t["major"] else 1
+        out.append((t["column"] - k // 2, 0, k, sc["tick_rows"], tuple(freq_line if t["major"] else minor) + (255,), H.OVL_OVER))
+    for t in sc["ticks"]:
+        out.append(design_text(glyphs, line_height, t["label"], t["column"], sc["label_row"], "center", "center", tuple(text) + (255,)))
+    hi, lo = design_db_labels(floor, ceil, fft_size, db_offset)
+    xr = min(int(88 * font_scale), W)
+    out.append(design_text(glyphs, line_height, hi, xr, 0, "right", "top", tuple(text) + (255,)))
+    out.append(design_text(glyphs, line_height, lo, xr, Hh, "right", "bottom", tuple(text) + (255,)))
+    for mk in markers:
+        m = design_demod_marker(mk["freq"], mk["bandwidth"], mk.get("sideband", "both"), freq, bandwidth, mk.get("flags", 0), W, Hh, mk.get("rgb", (255, 255, 255)))
+        out.append(m["prims"])
+        out.append(design_text(glyphs, line_height, m["prefix"] + mk.get("label", ""), m["label_x"], m["label_y"], m["halign"], "center", (255, 255, 255, 204)))
+    return overlay_prims(out)
+
+
+class OverlayBank:
+    """Ordered primitive lists -- grid rows, ticks, marker bands, glyphs -- composited onto the tiles of an atlas with WaterfallBank.view's geometry
+    in one launch (csdr_overlay).  The base picture is a host array, a DevicePointer to what a device_view returned, or nothing."""
+
+    def __init__(self, ctx, max_tiles=256, max_prims=1 << 16):
+        self._l = H.lib()
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        H.check(self._l.csdr_overlay_create(ctx.h, C.byref(self.h)))
+        self.setup(max_tiles, max_prims)
+
+    def setup(self, max_tiles, max_prims):
+        H.check(self._l.csdr_overlay_setup(self.h, int(max_tiles), int(max_prims)))
+        self.max_tiles, self.max_prims = int(max_tiles), int(max_prims)
+
+    def set_font(self, plane):
+        """plane: [font_h, font_w] uint8 coverage bytes, or None to remove the font"""
+        if plane is None:
+            H.check(self._l.csdr_overlay_set_font(self.h, None, 0, 0))
+            return
+        a = np.ascontiguousarray(plane, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError("a font plane is [height, width] bytes")
+        H.check(self._l.csdr_overlay_set_font(self.h, a.ctypes.data_as(C.c_void_p), a.shape[1], a.shape[0]))
+
+    @staticmethod
+    def pack(lists):
+        """one list per tile -> (prims, runs): the lists one behind the other"""
+        arrs = [overlay_prims([l]) if isinstance(l, np.ndarray) else overlay_prims(l) for l in lists]
+        at = np.concatenate([[0], np.cumsum([a.size for a in arrs])]).astype(int)
+        return overlay_prims(arrs), [(int(at[k]), int(arrs[k].size)) for k in range(len(arrs))]
+
+    def try_compose(self, prims, runs, width, height, atlas_cols=1, base=None, out=None, fetch=True):
+        """prims: PRIM_DTYPE array (overlay_prims); runs: one (first, count) per tile; base: None, a uint8 array of the picture's size or a
+        DevicePointer -> (return code, picture or None)"""
+        pr = np.ascontiguousarray(prims, dtype=PRIM_DTYPE).ravel()
+        tl = (H.OverlayTile * max(len(runs), 1))()
+        for k, (first, count) in enumerate(runs):
+            tl[k].first, tl[k].count = int(first), int(count)
+        n_tiles, cols = len(runs), int(atlas_cols)
+        if base is None:
+            bp, bdev, keep = None, 0, None
+        elif isinstance(base, DevicePointer):
+            bp, bdev, keep = C.c_void_p(base.ptr), 1, base
+        else:
+            keep = np.ascontiguousarray(base, dtype=np.uint8)
+            bp, bdev = keep.ctypes.data_as(C.c_void_p), 0
+        pp = pr.ctypes.data_as(C.POINTER(H.OverlayPrim)) if pr.size else None
+        if not fetch:
+            return self._l.csdr_overlay_compose(self.h, bp, bdev, tl, n_tiles, pp, pr.size, int(width), int(height), cols, None, 0), None
+        if out is None:
+            out = np.empty((max(-(-n_tiles // max(cols, 1)) * int(height), 0), max(cols * int(width), 0), 4), np.uint8)
+        rc = self._l.csdr_overlay_compose(self.h, bp, bdev, tl, n_tiles, pp, pr.size, int(width), int(height), cols, out.ctypes.data_as(C.c_void_p), out.nbytes)
+        return rc, out
+
+    def compose(self, prims, runs, width, height, atlas_cols=1, base=None, out=None, fetch=True):
+        """-> [tile rows * height, atlas_cols * width, 4] uint8; fetch=False composes it and leaves it on the device (device_view)"""
+        rc, pic = self.try_compose(prims, runs, width, height, atlas_cols, base, out, fetch)
+        H.check(rc)
+        return pic
+
+    def device_view(self):
+        """(device pointer, width, height) of the last composed picture in pixels; the context's boundary stream waits for it"""
+        p, w, h = C.c_void_p(), C.c_int(), C.c_int()
+        H.check(self._l.csdr_overlay_device_view(self.h, C.byref(p), C.byref(w), C.byref(h)))
+        return p.value, w.value, h.value
+
+    def close(self):
+        if self.h:
+            self._l.csdr_overlay_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class Distributor:
     """FFTDataDistributor's line cutting (csdr_distrib): the waterfall feed, cut where the block lies in HBM."""
 

@@ -107,6 +107,45 @@ class TraceItem(C.Structure):
     _fields_ = [("points", C.c_void_p), ("hold", C.c_void_p), ("n", C.c_int32), ("layout", C.c_int32), ("kind", C.c_int32), ("is_dev", C.c_int32)]
 
 
+OVL_OVER, OVL_ADD, OVL_COPY = range(3)
+ALIGN_LEFT, ALIGN_CENTER, ALIGN_RIGHT = range(3)
+ALIGN_TOP, ALIGN_BOTTOM = 0, 2
+SIDEBAND_BOTH, SIDEBAND_USB, SIDEBAND_LSB = range(3)
+MARKER_DELTA_LOCK, MARKER_RECORDING, MARKER_MUTED, MARKER_SOLO, MARKER_CENTERLINE = 1, 2, 4, 8, 16
+
+
+class OverlayPrim(C.Structure):
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("rgba", C.c_uint8 * 4), ("mode", C.c_int32), ("mask_x", C.c_int32),
+                ("mask_y", C.c_int32)]
+
+
+class OverlayTile(C.Structure):
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32)]
+
+
+class FreqTick(C.Structure):
+    _fields_ = [("m", C.c_double), ("value", C.c_double), ("major", C.c_int32), ("column", C.c_int32), ("label", C.c_char * 32)]
+
+
+class FreqScale(C.Structure):
+    _fields_ = [("step_mhz", C.c_double), ("tick_top", C.c_double), ("label_y", C.c_double), ("precision", C.c_int32), ("n_ticks", C.c_int32),
+                ("font_size", C.c_int32), ("tick_rows", C.c_int32), ("label_row", C.c_int32), ("pad", C.c_int32)]
+
+
+class DbGridRange(C.Structure):
+    _fields_ = [("alpha", C.c_double), ("step", C.c_double), ("first", C.c_int32), ("count", C.c_int32)]
+
+
+class DemodMarker(C.Structure):
+    _fields_ = [("ux", C.c_float), ("ofs_left", C.c_float), ("ofs_right", C.c_float), ("label_v", C.c_float), ("narrow", C.c_int32), ("halign", C.c_int32),
+                ("label_x", C.c_int32), ("label_y", C.c_int32), ("prefix", C.c_char * 8)]
+
+
+class Glyph(C.Structure):
+    _fields_ = [("id", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("xoffset", C.c_int32), ("yoffset", C.c_int32),
+                ("xadvance", C.c_int32)]
+
+
 class P2pOp(C.Structure):
     _fields_ = [("peer", C.c_int32), ("recv", C.c_int32), ("buf", C.c_void_p), ("n_samples", C.c_int64)]
 
@@ -386,6 +425,17 @@ ABI = {
     "csdr_tracebank_render": (_i, [_p, C.POINTER(TraceItem), _i, _i, _i, _i, _p, _i64]),
     "csdr_tracebank_device_view": (_i, [_p, _pp, C.POINTER(_i), C.POINTER(_i)]),
     "csdr_design_trace_envelope": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "csdr_overlay_create": (_i, [_p, _pp]),
+    "csdr_overlay_destroy": (None, [_p]),
+    "csdr_overlay_setup": (_i, [_p, _i, _i]),
+    "csdr_overlay_set_font": (_i, [_p, _p, _i, _i]),
+    "csdr_overlay_compose": (_i, [_p, _p, _i, C.POINTER(OverlayTile), _i, C.POINTER(OverlayPrim), _i, _i, _i, _i, _p, _i64]),
+    "csdr_overlay_device_view": (_i, [_p, _pp, C.POINTER(_i), C.POINTER(_i)]),
+    "csdr_design_freq_scale": (_i, [_i64, _i64, _i, _i, C.c_double, C.POINTER(FreqScale), C.POINTER(FreqTick), _i]),
+    "csdr_design_db_grid": (_i, [C.c_float, C.c_float, C.POINTER(DbGridRange), C.POINTER(_i), C.POINTER(C.c_double), _i]),
+    "csdr_design_db_labels": (_i, [C.c_float, C.c_float, _i, C.c_double, C.c_char_p, C.c_char_p, _i]),
+    "csdr_design_demod_marker": (_i, [_i64, _i, _i, _i64, _i64, _i, _i, _i, _p, C.POINTER(DemodMarker), C.POINTER(OverlayPrim), C.POINTER(_i)]),
+    "csdr_design_text": (_i, [C.POINTER(Glyph), _i, _i, C.c_char_p, _i, _i, _i, _i, _p, _i, C.POINTER(OverlayPrim), _i, C.POINTER(_i)]),
     "csdr_table_run": (_i, [_p, C.POINTER(Constellation), _p, _i, C.POINTER(DigitalState), _p, _i, C.POINTER(_i), C.POINTER(_f)]),
 }
 

@@ -52,6 +52,7 @@ typedef struct csdr_scopebank csdr_scopebank; /* N x ScopeVisualProcessor, one p
 typedef struct csdr_squelch csdr_squelch;     /* N x DemodulatorThread's level, floor, ceiling and squelch: every slot and block of an execute in one launch */
 typedef struct csdr_viewbank csdr_viewbank;   /* N x SpectrumVisualProcessor in zoomed view, one per demodulator: every slot and input of a call in one launch */
 typedef struct csdr_tracebank csdr_tracebank; /* the spectrum, hold and scope lines of any number of items as tiles of one RGBA8 atlas */
+typedef struct csdr_overlay csdr_overlay;     /* ordered primitive lists -- grid, ticks, markers, glyphs -- composited onto the tiles of an atlas in one launch */
 
 /* ------------------------------------------------------------------ context */
 int         csdr_abi_version(void);
@@ -1072,7 +1073,7 @@ int  csdr_viewbank_fetch_last(csdr_viewbank *vb, int slot, float *out, int cap_f
  *    bank's waveform items hold).
  *    CSDR_TRACE_SPECTRUM (SpectrumPanel.cpp:149-160): one polyline of n vertices; if `hold` is not NULL, a second one of n vertices in the same
  *      layout drawn over it: where the hold interval covers a pixel, out_c = (dst_c + hold_c + 1) >> 1 per colour channel (the reference's 0.5 alpha).
- *      The dB grid and the frequency labels stay out.
+ *      The dB grid and the frequency labels stay out of this object: they are csdr_overlay's ("Overlay bank" below).
  *    CSDR_TRACE_SCOPE_Y (ScopePanel.cpp:32-44, :97-99): one polyline; under it the row of y = 0 in the minor axis colour.
  *    CSDR_TRACE_SCOPE_2Y (:45-67, :100-105, constructor :7-16; height >= 2): an upper sub-panel of H / 2 rows and a lower one of H - H / 2.  The
  *      first n / 2 vertices are drawn in the upper one, the next n / 2 in the lower one, each as a polyline of n / 2 vertices over the full width;
@@ -1127,6 +1128,152 @@ int  csdr_tracebank_render(csdr_tracebank *tb, const csdr_trace_item *items, int
 int  csdr_tracebank_device_view(csdr_tracebank *tb, const uint8_t **dev, int *pic_width, int *pic_height);
 int  csdr_design_trace_envelope(const float *points, const float *hold_or_null, int n, int layout, int kind, int width, int height,
                                 int32_t *lo /*[2 width]*/, int32_t *hi /*[2 width]*/);
+
+/* ------------------------------------------------------------------ Overlay bank: grid, frequency scale, markers and labels on the tiles
+ * What tells a viewer what a tile shows: the dB grid (src/panel/SpectrumPanel.cpp:117-147), the frequency ticks with their MHz labels and the two dB
+ * labels (:171-303), and a marker and a label for every demodulator (PrimaryGLContext::DrawDemodInfo, src/visual/PrimaryGLContext.cpp:65-199).  A
+ * csdr_overlay composites ORDERED LISTS OF PRIMITIVES -- filled rectangles, optionally masked by a window of an 8-bit coverage plane (the glyphs of a
+ * font) -- onto the tiles of an atlas in ONE launch whatever the tile count; the csdr_design_* planners below turn the reference's numbers into such
+ * lists on the host, no device needed.  THE PICTURE IS THE LIBRARY'S OWN DEFINITION, all integer, and every implementation is held to it byte for byte.
+ * 1. Atlas: exactly csdr_wfbank_render's (item 6 of "Waterfall bank"): ceil(n_tiles / atlas_cols) * height rows by atlas_cols * width pixels, RGBA8,
+ *    tile k at tile row k / atlas_cols, tile column k % atlas_cols.  So tile k lies over tile k of csdr_tracebank_render / csdr_wfbank_render.
+ * 2. Base.  `base` is a picture of that very size and is never modified: host memory; with base_is_dev != 0 device memory, 4-byte aligned -- what
+ *    csdr_tracebank_device_view, csdr_wfbank_device_view or csdr_waterfall_device_view returned --; or NULL: all-zero bytes.  The output starts as the
+ *    base's bytes.  The unused tiles of the last tile row are zero bytes whatever the base holds; a tile with count == 0 is the base's bytes.
+ * 3. Lists.  tiles[k] = {first, count} names the run prims[first .. first + count) of the call's primitives as tile k's list; runs may overlap and
+ *    may be shared between tiles.  A primitive covers the pixels x <= px < x + w, y <= py < y + h of its tile (row 0 at the top) that lie inside the
+ *    tile: it may lie partly or wholly outside and is clipped; w == 0 or h == 0 draws nothing.
+ * 4. The rule.  For each pixel of a tile the primitives of its list that cover it are applied IN LIST ORDER to its four bytes d = (R, G, B, A), with
+ *    the primitive's colour bytes s = (rgba[0], rgba[1], rgba[2]) and its alpha a = rgba[3]:
+ *      a_eff = a                             without a mask (mask_x < 0);
+ *      a_eff = (a * cov + 127) / 255         with one, cov the font plane's byte at column mask_x + (px - x), row mask_y + (py - y): the window's
+ *                                            origin belongs to the primitive's UNCLIPPED origin, so a glyph cut by a tile edge keeps its shape.
+ *      CSDR_OVL_OVER  every byte: (s * a_eff + d * (255 - a_eff) + 127) / 255, with s = 255 for the A byte   (GL_SRC_ALPHA, GL_ONE_MINUS_SRC_ALPHA)
+ *      CSDR_OVL_ADD   every byte: min(255, d + (s * a_eff + 127) / 255), with s = 255 for the A byte         (GL_SRC_ALPHA, GL_ONE)
+ *      CSDR_OVL_COPY  R, G, B = s; A = a_eff
+ *    All divisions are integer divisions of non-negative numbers.  a_eff == 0 leaves OVER and ADD pixels as they are; a_eff == 255 makes OVER a copy.
+ * 5. Limits.  1 <= width, height <= 16384; 1 <= atlas_cols <= n_tiles <= max_tiles <= 2^20; 0 <= n_prims <= max_prims <= 2^22 (1 <= max_prims);
+ *    w, h >= 0; |x|, |y| <= 2^20.  CSDR_EINVAL, whole-call: a size out of range; a run not inside [0, n_prims] (first < 0, count < 0 or
+ *    first + count > n_prims); a mode out of range; w or h negative, |x| or |y| above 2^20; a masked primitive when no font is set, with mask_y < 0,
+ *    or whose window [mask_x, mask_x + w) x [mask_y, mask_y + h) leaves the font plane; a device base that is not 4-byte aligned.  CSDR_ERANGE:
+ *    n_tiles above max_tiles, n_prims above max_prims, a host buffer too small.  A refusal enqueues nothing and changes nothing: the last picture,
+ *    csdr_overlay_device_view and the font stay as they were.
+ * 6. Font.  csdr_overlay_set_font copies an 8-bit coverage plane of font_w x font_h bytes (1 .. 16384 each), dense, row 0 at the top, from host
+ *    memory to the device (synchronises).  The plane is caller data: the product ships no font and decodes no image.  a8 == NULL removes the font.
+ * 7. out_u8 == NULL leaves the picture on the device; csdr_overlay_device_view returns the last composed picture and its size in pixels and makes the
+ *    boundary stream wait for it; it stays valid until the next compose or setup.
+ * Ordering is the trace bank's.  All work runs on a stream of the object's own; a compose into host memory synchronises it.  The lists and a host base
+ * are copied into page-locked staging inside the call (two sets, used in turn), so the caller's buffers are free when it returns; a device base must
+ * have been produced on, or handed to, the boundary stream, is ordered behind it by an event and stays unchanged until the next synchronising call
+ * on this object.
+ *
+ * Planners (host only, no device; they set no csdr_last_error).  NDC -> pixels is ONE rule for all of them, in double, in a view of W x H pixels:
+ *      a horizontal boundary of u:            hb(u) = clamp(floor((u + 1) * 0.5 * W), 0, W)
+ *      a vertical boundary of v, from the top: vb(v) = clamp(floor((1 - v) * 0.5 * H), 0, H)
+ *    A rectangle between two boundaries is half-open -- columns [hb(u0), hb(u1)), rows [vb(v1), vb(v0)) for v0 < v1 -- so neighbours tile without gap
+ *    or overlap.  A vertical line of k pixels at u is the k columns from hb(u) - k / 2 (integer division), a horizontal line of one pixel at v the row
+ *    vb(v); both clipped to the view.  A float alpha or colour c becomes the byte (int)(c * 255 + 0.5).
+ * a. csdr_design_freq_scale (SpectrumPanel.cpp:171-277).  With the reference's types -- long long leftFreq = (double)freq - (double)bandwidth / 2.0
+ *    and rightFreq = leftFreq + (double)bandwidth, both truncated; LONG DOUBLE for mhzStep, mhzStart and currentMhz as the reference (the platform's
+ *    long double: 80-bit on x86-64); double for m; float for viewWidth and viewHeight --:  mhzStep = (100000 / (rightFreq - leftFreq)) * 2, visual step
+ *    0.1, precision 1.  While mhzStep * 0.5 * viewWidth < 40 * font_scale the ladder goes on to 0.25, 0.5, 1, 2.5, 5, 10 and 50 MHz (:184-216); else,
+ *    if it exceeds 350 * font_scale, the step is 0.01 MHz and the precision 2 (:217-221).  firstMhz = (leftFreq / 1000000) * 1000000 with truncating
+ *    division (:223), mhzStart = (firstMhz - leftFreq) / (rightFreq - leftFreq) * 2, currentMhz = trunc(floor(firstMhz / 1e6)).  The loop (:241-277)
+ *    runs m from -1 + mhzStart in steps of mhzStep while m <= 1 + |mhzStart|; below -1 it skips (adding the visual step to currentMhz), above 1 it
+ *    stops.  Per tick: m; value = currentMhz; label = "%.<precision>f" of it; major = (modf((double)currentMhz) < 0.001) (:255); column = hb(m).
+ *    A tick whose m is exactly -1 or 1 may fall either way (the sum m += mhzStep is rounded).  Also: tick_top = lMhzPos = 1 - 5 / viewHeight,
+ *    label_y = hPos = 1 - (16 / viewHeight) * font_scale and font_size 12, or 1 - (18 / viewHeight) * font_scale and 16 when viewHeight > 135, with
+ *    their rows tick_rows = vb(tick_top) (a tick fills rows [0, tick_rows)) and label_row = vb(label_y).  A major tick is 4 pixels wide (:256), a
+ *    minor one 1; the minor colour is 0.65 of the major one (:260).  bandwidth < 1, a view side outside 1 .. 16384, font_scale <= 0 or more than
+ *    2^20 loop turns: CSDR_EINVAL; more ticks than cap: CSDR_ERANGE with out->n_ticks the number needed.
+ * b. csdr_design_db_grid (:117-147).  range = ceil - floor in double from the two floats.  The three ranges {min, max, trans, step} = {90, 5000, 10,
+ *    100}, {20, 150, 10, 10}, {-20, 30, 10, 1}, in that order; one applies when min <= range <= max, with alpha 1, times (range - min) / trans when
+ *    range <= min + trans, times (trans - (range - (max - trans))) / trans when range >= max - trans.  Its positions: p starts at 0 and p += step / range
+ *    once per l = floor, floor + step, ... while l <= ceil + step; EVERY p is returned, in order, on the panel or not (0 <= p <= 1 is on it: p is the
+ *    height above the tile's bottom edge as a fraction of its height, the tile being the trace's panel, so its row is vb(2 p - 1)).  The colour is
+ *    0.12 grey, blended CSDR_OVL_ADD.  THE GRID IS ADDED OVER A FINISHED TRACE TILE, not under the trace as in the reference: the two differ only
+ *    where a trace pixel lies on a grid row.  floor or ceil not finite: CSDR_EINVAL; more positions than cap: CSDR_ERANGE.
+ * c. csdr_design_db_labels (:281-303): both strings are "%.1fdB" of db_offset + 20 log10(2 v / fft_size), v the float ceil or floor; both are empty
+ *    when ceil == floor or fft_size == 0.  (The gradient grounds of the two labels stay out.)
+ * d. csdr_design_demod_marker (PrimaryGLContext.cpp:89-164, :168-197), in float as the reference: uxPos = ((float)(demod_freq - (center_freq -
+ *    srate / 2)) / (float)srate - 0.5) * 2; ofs = (float)bandwidth / (float)srate; ofsLeft = 0 for CSDR_SIDEBAND_USB, ofsRight = 0 for
+ *    CSDR_SIDEBAND_LSB, else ofs; labelHeight = 20 / viewHeight, hPos = -1 + labelHeight.  Up to four primitives, in the reference's order, between
+ *    the columns hb(uxPos - ofsLeft) and hb(uxPos + ofsRight): the label ground, black at alpha 0.35, OVER, rows [vb(hPos + labelHeight), H) (:110-134);
+ *    the band in `rgb` at alpha 0.2, ADD, over the full height (:136-145); the same once more over the ground's rows when ofs * 2 < 16 / viewWidth
+ *    (:147-156: `narrow`); with CSDR_MARKER_CENTERLINE a one-pixel line at uxPos in `rgb` at alpha 0.5, ADD (:158-164).  The label: prefix "[" +
+ *    ("V" if _DELTA_LOCK) + ("R" if _RECORDING) + ("M" if _MUTED, else "S" if _SOLO) + "] ", empty when no letter applies (:168-187); anchored at
+ *    (label_x, label_y) = (hb(uxPos), vb(hPos)), vertically centred, horizontally left for USB, right for LSB, else centred (:191-197); white at
+ *    alpha 0.8, OVER.  The solo and recording tints of the label ground (:112-124) are GUI state and a clock and stay out.  srate < 1 or a view side
+ *    outside 1 .. 16384: CSDR_EINVAL.
+ * e. csdr_design_text lays one string out as masked primitives, by the library's own rule.  A csdr_glyph table is caller data with BMFont's
+ *    meaning: (x, y, w, h) the glyph's window in the plane, (xoffset, yoffset) from the pen and the line's top to the glyph's top-left, xadvance the
+ *    pen's step.  The string's bytes are looked up by id (the first match); a byte without a glyph is skipped (GLFont.cpp:597).  width = the sum
+ *    of the advances of the bytes that have a glyph.  pen starts at x (CSDR_ALIGN_LEFT), x - floor(width / 2) (_CENTER) or x - width (_RIGHT); the
+ *    line's top is y (CSDR_ALIGN_TOP), y - floor(line_height / 2) (_CENTER) or y - line_height (_BOTTOM).  Each glyph with w > 0 and h > 0 gives one
+ *    primitive {pen + xoffset, top + yoffset, w, h, rgba, mode, mask x, mask y}.  No scaling and no kerning: the reference stretches every glyph quad
+ *    to the line height and widens a space to the aspect of '_' (GLFont.cpp:488-495); that is not reproduced.  More primitives than cap: CSDR_ERANGE
+ *    with *n_out the number needed; a halign, valign or mode out of range, a negative w, h or line_height: CSDR_EINVAL. */
+#define CSDR_OVL_OVER 0
+#define CSDR_OVL_ADD  1
+#define CSDR_OVL_COPY 2
+typedef struct csdr_overlay_prim {
+    int32_t x, y, w, h;        /* tile pixels, row 0 at the top; may lie partly or wholly outside: clipped */
+    uint8_t rgba[4];           /* source colour and source alpha a */
+    int32_t mode;              /* CSDR_OVL_* */
+    int32_t mask_x, mask_y;    /* top-left of a w x h window of the font plane; mask_x < 0: no mask */
+} csdr_overlay_prim;
+typedef struct csdr_overlay_tile { int32_t first, count; } csdr_overlay_tile;   /* a run of the call's prims; runs may be shared between tiles */
+CSDR_STATIC_ASSERT(sizeof(csdr_overlay_prim) == 32 && offsetof(csdr_overlay_prim, rgba) == 16 && offsetof(csdr_overlay_prim, mask_x) == 24 &&
+                   sizeof(csdr_overlay_tile) == 8, "csdr_overlay_prim layout");
+int  csdr_overlay_create(csdr_ctx *ctx, csdr_overlay **out);
+void csdr_overlay_destroy(csdr_overlay *ov);
+int  csdr_overlay_setup(csdr_overlay *ov, int max_tiles, int max_prims);
+int  csdr_overlay_set_font(csdr_overlay *ov, const uint8_t *a8, int font_w, int font_h);
+int  csdr_overlay_compose(csdr_overlay *ov, const uint8_t *base, int base_is_dev, const csdr_overlay_tile *tiles, int n_tiles,
+                          const csdr_overlay_prim *prims, int n_prims, int width, int height, int atlas_cols, uint8_t *out_u8, int64_t cap);
+int  csdr_overlay_device_view(csdr_overlay *ov, const uint8_t **dev, int *pic_width, int *pic_height);
+
+#define CSDR_ALIGN_LEFT   0    /* halign */
+#define CSDR_ALIGN_CENTER 1    /* halign and valign */
+#define CSDR_ALIGN_RIGHT  2
+#define CSDR_ALIGN_TOP    0    /* valign */
+#define CSDR_ALIGN_BOTTOM 2
+#define CSDR_SIDEBAND_BOTH 0
+#define CSDR_SIDEBAND_USB  1
+#define CSDR_SIDEBAND_LSB  2
+#define CSDR_MARKER_DELTA_LOCK 1   /* flags of csdr_design_demod_marker */
+#define CSDR_MARKER_RECORDING  2
+#define CSDR_MARKER_MUTED      4
+#define CSDR_MARKER_SOLO       8
+#define CSDR_MARKER_CENTERLINE 16
+typedef struct csdr_freq_tick { double m, value; int32_t major, column; char label[32]; } csdr_freq_tick;
+typedef struct csdr_freq_scale {
+    double step_mhz;           /* the visual step: 0.01, 0.1, 0.25 ... 50 */
+    double tick_top, label_y;  /* lMhzPos and hPos, NDC */
+    int32_t precision;         /* digits of a label: 1, or 2 at the 0.01 step */
+    int32_t n_ticks;
+    int32_t font_size;         /* 12, or 16 when viewHeight > 135 */
+    int32_t tick_rows, label_row;  /* vb(tick_top), vb(label_y) */
+    int32_t pad;
+} csdr_freq_scale;
+typedef struct csdr_db_grid_range { double alpha, step; int32_t first, count; } csdr_db_grid_range;   /* positions p[first .. first + count) */
+typedef struct csdr_demod_marker {
+    float ux, ofs_left, ofs_right, label_v;   /* uxPos, ofsLeft, ofsRight, hPos */
+    int32_t narrow;                           /* ofs * 2 < 16 / viewWidth */
+    int32_t halign;                           /* CSDR_ALIGN_* of the label; its valign is CSDR_ALIGN_CENTER */
+    int32_t label_x, label_y;                 /* hb(uxPos), vb(hPos) */
+    char prefix[8];                           /* "" or "[..] " */
+} csdr_demod_marker;
+typedef struct csdr_glyph { int32_t id, x, y, w, h, xoffset, yoffset, xadvance; } csdr_glyph;
+CSDR_STATIC_ASSERT(sizeof(csdr_freq_tick) == 56 && sizeof(csdr_freq_scale) == 48 && sizeof(csdr_db_grid_range) == 24 && sizeof(csdr_demod_marker) == 40 &&
+                   sizeof(csdr_glyph) == 32, "planner record layouts");
+int  csdr_design_freq_scale(int64_t freq, int64_t bandwidth, int view_w, int view_h, double font_scale, csdr_freq_scale *out, csdr_freq_tick *ticks, int cap);
+int  csdr_design_db_grid(float floor_value, float ceil_value, csdr_db_grid_range *ranges /*[3]*/, int *n_ranges, double *p, int cap);
+int  csdr_design_db_labels(float floor_value, float ceil_value, int fft_size, double db_offset, char *ceil_label, char *floor_label, int cap /* bytes of each */);
+int  csdr_design_demod_marker(int64_t demod_freq, int bandwidth, int sideband, int64_t center_freq, int64_t srate, int flags, int view_w, int view_h,
+                              const uint8_t *rgb /*[3]*/, csdr_demod_marker *out, csdr_overlay_prim *prims /*[4]*/, int *n_prims);
+int  csdr_design_text(const csdr_glyph *glyphs, int n_glyphs, int line_height, const char *str, int x, int y, int halign, int valign,
+                      const uint8_t *rgba /*[4]*/, int mode, csdr_overlay_prim *out, int cap, int *n_out);
 
 /* ------------------------------------------------------------------ ingest
  * The reference's reader fills pooled SDRThreadIQData blocks (SoapySDRThread.cpp:221-225) and SDRPostThread hands ONE buffer to the
