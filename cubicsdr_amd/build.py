@@ -6,7 +6,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # one translation unit per object of include/csdr_hip.h (an edit rebuilds its own unit; the units compile in parallel)
-UNITS = ["csdr_ctx", "csdr_post", "csdr_bank", "csdr_spec", "csdr_io", "csdr_comm", "csdr_digital", "csdr_waterfall", "csdr_distrib", "csdr_specbank", "csdr_wfbank", "csdr_scopebank", "csdr_squelch", "csdr_viewbank", "csdr_tracebank", "csdr_overlay"]
+UNITS = ["csdr_ctx", "csdr_post", "csdr_bank", "csdr_spec", "csdr_io", "csdr_comm", "csdr_digital", "csdr_waterfall", "csdr_distrib", "csdr_specbank", "csdr_wfbank", "csdr_scopebank", "csdr_squelch", "csdr_viewbank", "csdr_tracebank", "csdr_overlay", "csdr_density"]
 SRCS = [os.path.join(HERE, "csrc", u + ".hip") for u in UNITS]
 OBJ_DIR = os.path.join(HERE, "csrc", "_obj")
 OUT = os.path.join(HERE, "libcsdr_hip.so")

@@ -15,7 +15,7 @@
 // every kernel has internal linkage: the kernel headers are included by several translation units (for the object layouts and constants next to
 // the kernels).  A kernel has ONE home unit, the one that launches it: csdr_post.hip (CSDR_TU_POST: channelizers, DC blocker), csdr_bank.hip
 // (CSDR_TU_BANK: front-ends, modems, audio), csdr_spec.hip (CSDR_TU_SPEC: the spectrum chain), csdr_io.hip (scope, mixer, ingest), csdr_waterfall.hip
-// (the raster; its switch sits in kernels_waterfall.hpp), csdr_distrib.hip (the waterfall feed; kernels_distrib.hpp), csdr_specbank.hip (the spectrum bank; kernels_specbank.hpp), csdr_scopebank.hip (the scope bank; kernels_scopebank.hpp), csdr_squelch.hip (the squelch bank; kernels_squelch.hpp), csdr_viewbank.hip (the view bank; kernels_viewbank.hpp), csdr_tracebank.hip (the trace bank; kernels_tracebank.hpp), csdr_overlay.hip (the overlay bank; kernels_overlay.hpp).  Elsewhere a
+// (the raster; its switch sits in kernels_waterfall.hpp), csdr_distrib.hip (the waterfall feed; kernels_distrib.hpp), csdr_specbank.hip (the spectrum bank; kernels_specbank.hpp), csdr_scopebank.hip (the scope bank; kernels_scopebank.hpp), csdr_squelch.hip (the squelch bank; kernels_squelch.hpp), csdr_viewbank.hip (the view bank; kernels_viewbank.hpp), csdr_tracebank.hip (the trace bank; kernels_tracebank.hpp), csdr_overlay.hip (the overlay bank; kernels_overlay.hpp), csdr_density.hip (the density bank; kernels_density.hpp).  Elsewhere a
 // kernel that is not a template already is declared as one that is never instantiated: parsed, not compiled (round 4 built chan_analyze_fft and the
 // demodulator kernels three times and the spectrum chain twice).
 #define CSDR_KERNEL static __global__
@@ -334,6 +334,7 @@ enum CsdrKernelId {
     KID_VIEWBANK,
     KID_TRACE_LINES, KID_TRACE_XY,
     KID_OVERLAY_COMPOSE,
+    KID_DENSITY_COVER, KID_DENSITY_FOLD, KID_DENSITY_RENDER,
     KID_COUNT
 };
 

@@ -152,7 +152,8 @@ static const char *kKernelNames[KID_COUNT] = {
     "squelch_scan", "squelch_pack", "squelch_pcm16",
     "viewbank_process",
     "trace_lines", "trace_xy",
-    "overlay_compose"};
+    "overlay_compose",
+    "density_cover", "density_fold", "density_render"};
 static int prof_drain(csdr_ctx *c) {
     if (int rc = c->sync_all()) return rc;
     std::lock_guard<std::mutex> lk(c->prof_mu);

@@ -1030,6 +1030,141 @@ class TraceBank:
             self.h = C.c_void_p()
 
 
+def design_density_cover(points, width, height, n, frames=1, kind="spectrum", layout=0, stride_floats=None):
+    """how many of the frames pass through every pixel of a width x height tile (host only; csdr_hip.h, "Density bank", item 1) -> uint32 [height, width]"""
+    a = np.ascontiguousarray(points, dtype=np.float32).ravel()
+    stride = int(n) * (1 + int(layout)) if stride_floats is None else int(stride_floats)
+    cover = np.empty((max(int(height), 0), max(int(width), 0)), np.uint32)
+    H.check(H.lib().csdr_design_density_cover(a.ctypes.data_as(C.c_void_p) if a.size else None, int(n), int(layout), stride, int(frames), _trace_kind(kind),
+                                              int(width), int(height), cover.ctypes.data_as(C.c_void_p)))
+    return cover
+
+
+def density_palette(stops, alpha=255):
+    """a 256-entry RGBA palette for DensityBank.set_palette from colour stops [[r, g, b], ...] in 0 .. 1 (csdr_design_gradient) -> uint8 [256, 4]"""
+    r, g, b = design_gradient(stops, 256)
+    pal = np.empty((256, 4), np.uint8)
+    for k, ch in enumerate((r, g, b)):
+        pal[:, k] = np.clip(np.floor(ch.astype(np.float64) * 255.0 + 0.5), 0, 255).astype(np.uint8)
+    pal[:, 3] = int(alpha)
+    return pal
+
+
+class DensityBank:
+    """The persistence display (csdr_density): one uint32 hit grid per slot in HBM -- how often the trace passed through every pixel of a
+    width x height tile -- stepped with ALL frames of its items in two launches and drawn through a palette as tiles of one RGBA8 atlas with
+    WaterfallBank.view's geometry.  Points are read where they lie in HBM."""
+
+    def __init__(self, ctx, width, height, max_slots=1, max_frames=1024, max_points=1 << 16):
+        self._l = H.lib()
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        H.check(self._l.csdr_density_create(ctx.h, C.byref(self.h)))
+        self.setup(width, height, max_slots, max_frames, max_points)
+
+    def setup(self, width, height, max_slots, max_frames, max_points):
+        H.check(self._l.csdr_density_setup(self.h, int(width), int(height), int(max_slots), int(max_frames), int(max_points)))
+        self.width, self.height, self.max_slots, self.max_frames, self.max_points = int(width), int(height), int(max_slots), int(max_frames), int(max_points)
+
+    def set_palette(self, rgba):
+        """rgba: uint8 [256, 4]"""
+        a = np.ascontiguousarray(rgba, dtype=np.uint8).reshape(256, 4)
+        H.check(self._l.csdr_density_set_palette(self.h, a.ctypes.data_as(C.c_void_p)))
+
+    def reset_slot(self, slot):
+        H.check(self._l.csdr_density_reset_slot(self.h, int(slot)))
+
+    def try_step(self, items):
+        """items: dicts with slot, points (a numpy float32 array, a DevicePointer or None: decay only), n (default: what one frame of the points
+        holds), frames (default 1), layout (0 | 1), kind ("spectrum" | "y"), stride_floats (default n * (1 + layout)), keep_q16 (default 65536),
+        weight (default 1) -> return code"""
+        arr = (H.DensityItem * max(len(items), 1))()
+        keep = []
+        for k, it in enumerate(items):
+            layout, frames = int(it.get("layout", 0)), int(it.get("frames", 1))
+            p = it.get("points")
+            ptr, dev, floats = None, 0, 0
+            if isinstance(p, DevicePointer):
+                keep.append(p)
+                ptr, dev, floats = p.ptr, 1, p.n
+            elif p is not None:
+                a = np.ascontiguousarray(p, dtype=np.float32).ravel()
+                keep.append(a)
+                ptr, floats = (a.ctypes.data if a.size else None), a.size
+            n = it.get("n")
+            if n is None:
+                n = floats // max(frames, 1) // (1 + (layout & 1))
+            stride = it.get("stride_floats")
+            arr[k].points, arr[k].slot, arr[k].n, arr[k].frames, arr[k].layout = ptr, int(it["slot"]), int(n), frames, layout
+            arr[k].stride_floats = int(n) * (1 + layout) if stride is None else int(stride)
+            arr[k].kind, arr[k].is_dev = _trace_kind(it.get("kind", "spectrum")), dev
+            arr[k].keep_q16, arr[k].weight = int(it.get("keep_q16", 65536)), int(it.get("weight", 1))
+        return self._l.csdr_density_step(self.h, arr, len(items))
+
+    def step(self, items):
+        H.check(self.try_step(items))
+
+    def step_spec(self, slot, spec, frame0=0, n_frames=None, keep_q16=65536, weight=1):
+        """frames [frame0, frame0 + n_frames) (default: all from frame0) of a SpectrumProcessor's last process, hideDC as its fetch applies it"""
+        if n_frames is None:
+            n_frames = self._l.csdr_spec_frames(spec.h) - int(frame0)
+        H.check(self._l.csdr_density_step_spec(self.h, int(slot), spec.h, int(frame0), int(n_frames), int(keep_q16), int(weight)))
+
+    def step_specbank(self, bank, keep_q16=65536, weight=1):
+        """slot s takes all frames of slot s of a SpectrumBank's last process"""
+        H.check(self._l.csdr_density_step_specbank(self.h, bank.h, int(keep_q16), int(weight)))
+
+    def step_views(self, viewbank, slots=None, keep_q16=65536, weight=1):
+        """slot s takes all frames of slot s of a ViewBank's last process, read where they lie in HBM (viewbank.device_points).  A slot without frames
+        only decays.  The caller synchronises this object (fetch, peak or a fetched render) before the view bank's next process."""
+        items = []
+        for s in (range(min(self.max_slots, viewbank.max_slots)) if slots is None else slots):
+            p, frames = viewbank.device_points(s)
+            pts = DevicePointer(p, frames * viewbank.fft_size) if frames > 0 else None
+            items.append(dict(slot=s, points=pts, n=viewbank.fft_size, frames=max(frames, 0), keep_q16=keep_q16, weight=weight))
+        self.step(items)
+
+    def peak(self, slot):
+        v = C.c_uint32()
+        H.check(self._l.csdr_density_peak(self.h, int(slot), C.byref(v)))
+        return v.value
+
+    def fetch(self, slot):
+        """-> the slot's counts, uint32 [height, width]"""
+        out = np.empty((self.height, self.width), np.uint32)
+        H.check(self._l.csdr_density_fetch(self.h, int(slot), out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def try_render(self, views, atlas_cols=1, out=None, fetch=True):
+        """views: (slot, full) pairs or plain slots (full = 0: the slot's peak); slot -1: an all-zero tile -> (return code, picture or None)"""
+        arr = (H.DensityView * max(len(views), 1))()
+        for k, v in enumerate(views):
+            arr[k].slot, arr[k].full = (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), 0)
+        n, cols = len(views), int(atlas_cols)
+        if not fetch:
+            return self._l.csdr_density_render(self.h, arr, n, cols, None, 0), None
+        if out is None:
+            out = np.empty((max(-(-n // max(cols, 1)) * self.height, 0), max(cols * self.width, 0), 4), np.uint8)
+        return self._l.csdr_density_render(self.h, arr, n, cols, out.ctypes.data_as(C.c_void_p), out.nbytes), out
+
+    def render(self, views, atlas_cols=1, out=None, fetch=True):
+        """-> [tile rows * height, atlas_cols * width, 4] uint8; fetch=False renders it and leaves it on the device (device_view)"""
+        rc, pic = self.try_render(views, atlas_cols, out, fetch)
+        H.check(rc)
+        return pic
+
+    def device_view(self):
+        """(device pointer, width, height) of the last rendered picture in pixels; the context's boundary stream waits for it"""
+        p, w, h = C.c_void_p(), C.c_int(), C.c_int()
+        H.check(self._l.csdr_density_device_view(self.h, C.byref(p), C.byref(w), C.byref(h)))
+        return p.value, w.value, h.value
+
+    def close(self):
+        if self.h:
+            self._l.csdr_density_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 PRIM_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("rgba", "u1", (4,)), ("mode", "<i4"), ("mask_x", "<i4"), ("mask_y", "<i4")])
 GLYPH_DTYPE = np.dtype([(k, "<i4") for k in ("id", "x", "y", "w", "h", "xoffset", "yoffset", "xadvance")])
 OVL_MODES = {"over": H.OVL_OVER, "add": H.OVL_ADD, "copy": H.OVL_COPY}

@@ -107,6 +107,15 @@ class TraceItem(C.Structure):
     _fields_ = [("points", C.c_void_p), ("hold", C.c_void_p), ("n", C.c_int32), ("layout", C.c_int32), ("kind", C.c_int32), ("is_dev", C.c_int32)]
 
 
+class DensityItem(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("stride_floats", C.c_int64), ("slot", C.c_int32), ("n", C.c_int32), ("frames", C.c_int32), ("layout", C.c_int32),
+                ("kind", C.c_int32), ("is_dev", C.c_int32), ("keep_q16", C.c_uint32), ("weight", C.c_uint32)]
+
+
+class DensityView(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("full", C.c_uint32)]
+
+
 OVL_OVER, OVL_ADD, OVL_COPY = range(3)
 ALIGN_LEFT, ALIGN_CENTER, ALIGN_RIGHT = range(3)
 ALIGN_TOP, ALIGN_BOTTOM = 0, 2
@@ -436,6 +445,19 @@ ABI = {
     "csdr_design_db_labels": (_i, [C.c_float, C.c_float, _i, C.c_double, C.c_char_p, C.c_char_p, _i]),
     "csdr_design_demod_marker": (_i, [_i64, _i, _i, _i64, _i64, _i, _i, _i, _p, C.POINTER(DemodMarker), C.POINTER(OverlayPrim), C.POINTER(_i)]),
     "csdr_design_text": (_i, [C.POINTER(Glyph), _i, _i, C.c_char_p, _i, _i, _i, _i, _p, _i, C.POINTER(OverlayPrim), _i, C.POINTER(_i)]),
+    "csdr_density_create": (_i, [_p, _pp]),
+    "csdr_density_destroy": (None, [_p]),
+    "csdr_density_setup": (_i, [_p, _i, _i, _i, _i, _i]),
+    "csdr_density_set_palette": (_i, [_p, _p]),
+    "csdr_density_reset_slot": (_i, [_p, _i]),
+    "csdr_density_step": (_i, [_p, C.POINTER(DensityItem), _i]),
+    "csdr_density_step_spec": (_i, [_p, _i, _p, _i, _i, C.c_uint32, C.c_uint32]),
+    "csdr_density_step_specbank": (_i, [_p, _p, C.c_uint32, C.c_uint32]),
+    "csdr_density_peak": (_i, [_p, _i, C.POINTER(C.c_uint32)]),
+    "csdr_density_fetch": (_i, [_p, _i, _p, _i64]),
+    "csdr_density_render": (_i, [_p, C.POINTER(DensityView), _i, _i, _p, _i64]),
+    "csdr_density_device_view": (_i, [_p, _pp, C.POINTER(_i), C.POINTER(_i)]),
+    "csdr_design_density_cover": (_i, [_p, _i, _i, _i64, _i, _i, _i, _i, _p]),
     "csdr_table_run": (_i, [_p, C.POINTER(Constellation), _p, _i, C.POINTER(DigitalState), _p, _i, C.POINTER(_i), C.POINTER(_f)]),
 }
 

@@ -53,6 +53,7 @@ typedef struct csdr_squelch csdr_squelch;     /* N x DemodulatorThread's level, 
 typedef struct csdr_viewbank csdr_viewbank;   /* N x SpectrumVisualProcessor in zoomed view, one per demodulator: every slot and input of a call in one launch */
 typedef struct csdr_tracebank csdr_tracebank; /* the spectrum, hold and scope lines of any number of items as tiles of one RGBA8 atlas */
 typedef struct csdr_overlay csdr_overlay;     /* ordered primitive lists -- grid, ticks, markers, glyphs -- composited onto the tiles of an atlas in one launch */
+typedef struct csdr_density csdr_density;     /* N hit grids in HBM: how often the trace passed through every pixel of a tile, drawn through a palette */
 
 /* ------------------------------------------------------------------ context */
 int         csdr_abi_version(void);
@@ -1274,6 +1275,88 @@ int  csdr_design_demod_marker(int64_t demod_freq, int bandwidth, int sideband, i
                               const uint8_t *rgb /*[3]*/, csdr_demod_marker *out, csdr_overlay_prim *prims /*[4]*/, int *n_prims);
 int  csdr_design_text(const csdr_glyph *glyphs, int n_glyphs, int line_height, const char *str, int x, int y, int halign, int valign,
                       const uint8_t *rgba /*[4]*/, int mode, csdr_overlay_prim *out, int cap, int *n_out);
+
+/* ------------------------------------------------------------------ Density bank: spectrum persistence as RGBA tiles
+ * The persistence ("digital phosphor") display: for every pixel of a spectrum or scope tile, how often the trace passed through it.  The reference
+ * has the idea only as ScopePanel's 0.05-alpha background (src/panel/ScopePanel.cpp:88-89), which "Trace bank" item 4 leaves out.  A csdr_density
+ * is a bank of max_slots independent hit grids in HBM, uint32 count[height][width] each, with the tile geometry of csdr_wfbank_render; a step
+ * rasterises ALL frames of every listed item -- read where the spectrum, view and scope banks left them in HBM, or given on the host -- and a render
+ * maps the counts through a palette.  Every step runs the same two launches and every render the same one launch, whatever the slot, item and
+ * frame counts.  THE PICTURE IS THE LIBRARY'S OWN DEFINITION: after the trace bank's one float step per vertex everything is exact integer
+ * arithmetic, and every implementation is held to it count for count and byte for byte.
+ * 1. Cover of a frame.  A frame is a polyline of n vertices of kind CSDR_TRACE_SPECTRUM or CSDR_TRACE_SCOPE_Y, layout 0 (n y values) or 1 (n (x, y)
+ *    pairs).  Its cover is the LINE interval [lo_c, hi_c] of every column c of a tile width x height, exactly as "Trace bank" items 1 - 3 define it:
+ *    what csdr_design_trace_envelope(points, NULL, n, layout, kind, width, height, lo, hi) writes into lo[0 .. width) and hi[0 .. width).  The scope's
+ *    axis rows are not part of the cover; the other kinds are CSDR_EINVAL.  An item holds `frames` frames, frame f at points + f * stride_floats, and
+ *    cover[r][c] is the number of its frames f with lo_c(f) <= r <= hi_c(f).  Rows [0, 9, 0] at width 7, height 10, one frame: cover is 1 exactly on
+ *    lo = [0, 2, 7, 2, 0, -, -] .. hi = [2, 7, 9, 7, 2, -, -].
+ * 2. Step.  csdr_density_step takes a list of items; for every cell of a slot the list names, evaluated in 64 bits,
+ *        count' = min(2^32 - 1, floor(count * keep_q16 / 65536) + weight * cover)
+ *    with 0 <= keep_q16 <= 65536 and 1 <= weight <= 2^24.  An item with points == NULL, n == 0 or frames == 0 only decays (cover = 0).  Slots the list
+ *    does not name keep their state; a slot named twice in one list is CSDR_EINVAL.  A slot starts all-zero; csdr_density_reset_slot restores that.
+ * 3. Peak.  peak[slot] is the maximum count of the slot after its last step (0 for a fresh or reset slot); csdr_density_peak synchronises.
+ * 4. Render.  Views {slot, full}; tile k of the atlas is exactly csdr_wfbank_render's (item 6 of "Waterfall bank"): ceil(n_views / atlas_cols) * height
+ *    rows by atlas_cols * width pixels, view k at tile row k / atlas_cols, tile column k % atlas_cols.  slot == -1 gives an all-zero tile, and the
+ *    unused tiles of the last tile row are all-zero.  Per pixel, with full_eff = full ? full : max(peak[slot], 1):
+ *        idx = 0 when count == 0;  idx = 255 when count >= full_eff;  otherwise idx = max(1, floor(count * 255 / full_eff)), in 64 bits
+ *    and the four bytes of the pixel are palette[idx].  csdr_density_set_palette sets the 256 x RGBA palette, one per object; before any call it is
+ *    (i, i, i, 255).  A cell that was hit is never drawn with index 0.  out_u8 == NULL leaves the picture on the device; csdr_density_device_view
+ *    returns the last rendered picture and its size in pixels with the trace bank's rules (valid until the next render or setup), so a csdr_overlay
+ *    takes it as its base.
+ * 5. Readers in HBM.  csdr_density_step_spec steps `slot` with frames [frame0, frame0 + n_frames) of a spectrum's last process as ONE item of kind
+ *    CSDR_TRACE_SPECTRUM with n = the spectrum's fftSize: vertex i of a frame is the point csdr_spec_fetch would return at i, the DC-spike overwrite
+ *    of csdr_spec_set_hide_dc included.  csdr_density_step_specbank steps slot s with the csdr_specbank_frames(sb, s) frames of slot s of a
+ *    spectrum bank's last process, for every s below the smaller of the two slot counts (a slot without frames only decays), n = the bank's fftSize.  Both
+ *    order themselves against the producer by events, as csdr_waterfall_step_spec and csdr_wfbank_step_specbank do: nothing waits on the host and
+ *    the producer's next process waits for the reads.  View-bank and scope-bank points come in as items with is_dev = 1, from
+ *    csdr_viewbank_device_points / csdr_scopebank_device_points.
+ * 6. Limits.  2 <= width <= 16384, 1 <= height <= 2048, max_slots >= 1 and max_slots * height * width <= 2^30, 1 <= max_frames <= 2^20,
+ *    1 <= max_points <= 2^21, 1 <= n_items <= max_slots, 1 <= atlas_cols <= n_views <= 2^20.  A kind other than the two, a layout other than 0 | 1,
+ *    n < 0, frames < 0, is_dev other than 0 | 1, a slot out of range or named twice, stride_floats below n * (1 + layout) where frames are read,
+ *    keep_q16 above 65536, weight 0 or above 2^24, device points that are not 4-byte aligned: CSDR_EINVAL.  frames above max_frames, n above
+ *    max_points, a host buffer too small: CSDR_ERANGE.  A refusal changes nothing.
+ * 7. csdr_design_density_cover is item 1 on the host, no device needed: cover[height][width], uint32, is overwritten.
+ * Ordering is the trace bank's.  All work runs on a stream of the object's own; csdr_density_fetch, csdr_density_peak and a render into host memory
+ * synchronise it.  Host points are copied into page-locked staging inside the call, so the caller's buffers are free when it returns.  Device points
+ * must have been produced on, or handed to, the boundary stream -- what csdr_specbank_device_points, csdr_viewbank_device_points and
+ * csdr_scopebank_device_points do -- are ordered behind it by an event and stay unchanged until the next synchronising call on this object.
+ * csdr_density_device_view makes the boundary stream wait for the picture.  The producing banks are not touched and wait for nobody here: a caller
+ * who steps from device points synchronises this object -- csdr_density_fetch, csdr_density_peak or a render into host memory -- before the
+ * producer's next process, the rule those device_points calls give every reader.  A call waits on the host only for the upload of its records that
+ * last used the same page-locked staging set, two calls ago. */
+typedef struct csdr_density_item {
+    const float *points;       /* the frames' vertices; NULL: the slot only decays */
+    int64_t stride_floats;     /* from the first float of a frame to the first float of the next; >= n * (1 + layout) */
+    int32_t slot;              /* the slot the item updates */
+    int32_t n;                 /* vertices per frame; 0: the slot only decays */
+    int32_t frames;            /* frames; 0: the slot only decays */
+    int32_t layout;            /* 0: y values; 1: (x, y) pairs */
+    int32_t kind;              /* CSDR_TRACE_SPECTRUM | CSDR_TRACE_SCOPE_Y */
+    int32_t is_dev;            /* 1: `points` is device memory, 4-byte aligned */
+    uint32_t keep_q16;         /* decay factor, 0 .. 65536 */
+    uint32_t weight;           /* hits one frame adds, 1 .. 2^24 */
+} csdr_density_item;
+CSDR_STATIC_ASSERT(sizeof(csdr_density_item) == 48 && offsetof(csdr_density_item, stride_floats) == 8 && offsetof(csdr_density_item, slot) == 16 &&
+                   offsetof(csdr_density_item, is_dev) == 36 && offsetof(csdr_density_item, weight) == 44, "csdr_density_item layout");
+typedef struct csdr_density_view {
+    int32_t slot;              /* -1: an all-zero tile */
+    uint32_t full;             /* the count drawn with palette[255]; 0: the slot's peak */
+} csdr_density_view;
+CSDR_STATIC_ASSERT(sizeof(csdr_density_view) == 8 && offsetof(csdr_density_view, full) == 4, "csdr_density_view layout");
+int  csdr_density_create(csdr_ctx *ctx, csdr_density **out);
+void csdr_density_destroy(csdr_density *db);
+int  csdr_density_setup(csdr_density *db, int width, int height, int max_slots, int max_frames, int max_points);     /* every slot all-zero */
+int  csdr_density_set_palette(csdr_density *db, const uint8_t *rgba /*[256][4]*/);
+int  csdr_density_reset_slot(csdr_density *db, int slot);
+int  csdr_density_step(csdr_density *db, const csdr_density_item *items, int n_items);
+int  csdr_density_step_spec(csdr_density *db, int slot, csdr_spec *spec, int frame0, int n_frames, uint32_t keep_q16, uint32_t weight);
+int  csdr_density_step_specbank(csdr_density *db, csdr_specbank *sb, uint32_t keep_q16, uint32_t weight);
+int  csdr_density_peak(csdr_density *db, int slot, uint32_t *peak);
+int  csdr_density_fetch(csdr_density *db, int slot, uint32_t *out /*[height][width]*/, int64_t cap /* entries */);
+int  csdr_density_render(csdr_density *db, const csdr_density_view *views, int n_views, int atlas_cols, uint8_t *out_u8, int64_t cap);
+int  csdr_density_device_view(csdr_density *db, const uint8_t **dev, int *pic_width, int *pic_height);
+int  csdr_design_density_cover(const float *points, int n, int layout, int64_t stride_floats, int frames, int kind, int width, int height,
+                               uint32_t *cover /*[height][width]*/);
 
 /* ------------------------------------------------------------------ ingest
  * The reference's reader fills pooled SDRThreadIQData blocks (SoapySDRThread.cpp:221-225) and SDRPostThread hands ONE buffer to the
